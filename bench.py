@@ -7,12 +7,19 @@ A "step" = one Gram build K = SpdAffineInvariantGaussianKernel(X, X) on a synthe
 `symmetric_gram`, it is not `value`).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR
     python bench.py --gpus N ...                 (spawns its N ranks itself through torch.distributed.run, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Multi-GPU: the path shards by independent Gram builds (one point set per rank, no data-path collective) -> "weak".
 Prints ONE JSON line on rank 0.  `roofline` is the binding resource of the dominant kernel (fp64 issue, flop model of SURVEY 8d);
 the streaming-byte model the scope contract also names is reported under `roofline_hbm_streaming_model` and marked non-physical.
+
+A plain run does only what the headline needs: set-up, preheat and warm-up, the K timed steps, the outputs if --dump-outputs is given,
+the line.  Everything else - the x1-is-x2 build, the kernel classes' forward timings, the acquisition sweeps, the other BASELINE configs,
+the backward and the surrogate fit, the parity gates against the oracle, the rocprofv3 HBM-traffic passes, the CPU baseline and, with
+several ranks, the collective self-check and the sharded Gram - runs with --full.
 """
 import argparse
 import json
@@ -36,6 +43,7 @@ BYTES_PER_PAIR = 2 * DIM * DIM * 8 + 8                 # SURVEY 8(d) streaming m
 FLOP_PER_PAIR = (10.0 / 3.0) * DIM ** 3 + 30.0 * DIM ** 2   # congruence + tridiagonalisation + QL
 HBM_PEAK_GBS = 8000.0
 FP64_PEAK_TFLOPS = 78.6
+DUMP_ROWS = 1024                    # --dump-outputs: 1024 x 4096 fp64 = 32 MiB of the 128 MiB Gram
 
 
 def synthetic_spd_mandel(n, d, seed):
@@ -546,13 +554,20 @@ def main():
                     "20th on, profiles/pmc_summary.json); reported in the line as `untimed_preheat_steps`")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--traffic", choices=["auto", "measure", "file"], default="auto", help="roofline.traffic: measured in this run with two rocprofv3 "
-                    "--pmc passes (auto: when rocprofv3 is on PATH, one rank, not already under a profiler; ~30 s) or read from profiles/pmc_summary.json")
+                    "--pmc passes (auto: with --full, when rocprofv3 is on PATH, one rank, not already under a profiler; ~30 s) or read from "
+                    "profiles/pmc_summary.json")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--sweep-lite", action="store_true", help="only the single-launch-solve variants of the config-4 sweep (tests: the eight-rank run on one device)")
     ap.add_argument("--no-plugin-surface", action="store_true", help="skip the kernel classes' forward timings (profiling runs)")
     ap.add_argument("--no-symmetric", action="store_true", help="skip the separately reported x1-is-x2 run (profiling: keeps "
                     "the rocprof average of the pairwise kernel equal to the `value` launches)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline (see the module docstring); "
+                    "the --no-* options and --sweep-lite select within it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed on rank 0 to DIR/gram_rows.npy: "
+                    f"{DUMP_ROWS} rows of the {N_POINTS} x {N_POINTS} Gram (a fixed seeded sample, ascending), float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -577,7 +592,7 @@ def main():
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)
     backend = "none" if dist is None else str(dist.get_backend())
-    collectives = None if dist is None else _collective_selfcheck(dist, device, world, rank)
+    collectives = None if dist is None or not args.full else _collective_selfcheck(dist, device, world, rank)
 
     x = synthetic_spd_mandel(N_POINTS, DIM, 1234 + rank)      # one independent point set per rank
     job = GramJob(x, device, symmetric=False)
@@ -588,17 +603,21 @@ def main():
     st = job.status.tolist()
     if st[0] != 0:
         raise RuntimeError(f"device status {st}")
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        rows = np.sort(np.random.default_rng(0).choice(N_POINTS, DUMP_ROWS, replace=False))
+        np.save(os.path.join(args.dump_outputs, "gram_rows.npy"), job.out[torch.from_numpy(rows).to(device)].cpu().numpy())
     sym, sym_ms = None, None
-    if not args.no_symmetric:
+    if args.full and not args.no_symmetric:
         sym = GramJob(x, device, symmetric=True)
         _, sym_ms, _ = timed(sym, args.steps, args.warmup, None)
 
     plugin = None
-    if rank == 0 and world == 1 and not args.no_plugin_surface:
+    if args.full and rank == 0 and world == 1 and not args.no_plugin_surface:
         plugin = plugin_surface_timings(device, x, ev_ms, args.steps)
 
     sharded = None
-    if world > 1:
+    if args.full and world > 1:
         # strong scaling of ONE N=4096 Gram: row blocks over the ranks, left sharded or assembled with one all_gather
         from gabotorch_amd import ops as _ops
         from gabotorch_amd.distributed import sharded_gram
@@ -624,7 +643,7 @@ def main():
                    "parity_max_abs_vs_unsharded": err_sh}
 
     sweep = None
-    if not args.no_sweep:
+    if args.full and not args.no_sweep:
         # config 4 (gabo_spd S^5_++, 512 restarts): lock-step trust regions, restarts sharded r % world over the ranks,
         # one all_gather + argmax (RCCL).  Reported beside the headline metric, never mixed into `value`.
         from tools.sweep_bench import run_sweep
@@ -784,7 +803,7 @@ def main():
 
 
     sphere_sweep_result = None
-    if not args.no_sweep:
+    if args.full and not args.no_sweep:
         # the sphere counterpart of the sweep (gabo_sphere's setting: stock trust regions with EXACT Hessian-vector products, no
         # constraints): GP(50 obs) + EI on S^9, 512 restarts sharded over the ranks - one launch for the whole solve (csrc/sphere_tr.hip).
         # Every rank takes part: the maximiser broadcasts / all_gathers when torch.distributed is initialised.
@@ -823,22 +842,25 @@ def main():
     value = world * pairs_per_step * args.steps / wall_max
 
     if rank == 0:
-        # correctness gate inside the bench: a 256 x 256 block against the oracle
-        from oracle import spd as ospd
-        blk = job.out[:256, :256].cpu().numpy()
-        want = ospd.spd_ai_gaussian_kernel(x[:256], x[:256], BETA)
-        max_rel = float(np.max(np.abs(blk - want) / np.abs(want)))
-        max_rel_sym = 0.0
-        if sym is not None:
-            sym_blk = sym.out[:256, :256].cpu().numpy()
-            max_rel_sym = float(np.max(np.abs(sym_blk - want) / np.abs(want)))
-        if not (max_rel < 1e-5 and max_rel_sym < 1e-5):
-            raise RuntimeError(f"parity gate failed: {max_rel} {max_rel_sym}")
+        parity = None
+        if args.full:
+            # correctness gate inside the bench: a 256 x 256 block against the oracle
+            from oracle import spd as ospd
+            blk = job.out[:256, :256].cpu().numpy()
+            want = ospd.spd_ai_gaussian_kernel(x[:256], x[:256], BETA)
+            max_rel = float(np.max(np.abs(blk - want) / np.abs(want)))
+            max_rel_sym = 0.0
+            if sym is not None:
+                sym_blk = sym.out[:256, :256].cpu().numpy()
+                max_rel_sym = float(np.max(np.abs(sym_blk - want) / np.abs(want)))
+            if not (max_rel < 1e-5 and max_rel_sym < 1e-5):
+                raise RuntimeError(f"parity gate failed: {max_rel} {max_rel_sym}")
+            parity = {"max_rel_err_vs_oracle_256x256": max_rel, "symmetric": max_rel_sym, "tolerance": 1e-5}
         kernel_s = ev_ms * 1e-3               # prep + pairwise launches; the pairwise kernel is > 99.5 % of it (profiles/)
         ach_gbs = pairs_per_step * BYTES_PER_PAIR / kernel_s / 1e9
         ach_tf = pairs_per_step * FLOP_PER_PAIR / kernel_s / 1e12
         traffic, traffic_source = None, None
-        if args.traffic != "file" and world == 1:
+        if (args.traffic == "measure" or (args.traffic == "auto" and args.full)) and world == 1:
             traffic, traffic_source = measure_hbm_traffic()
             if traffic is None and args.traffic == "measure":
                 raise RuntimeError(f"--traffic measure: {traffic_source}")
@@ -878,7 +900,7 @@ def main():
             "symmetric_gram": None if sym is None else {
                 "ms_per_step": sym_ms, "pairs_per_s": pairs_per_step / (sym_ms * 1e-3),
                 "note": "x1 is x2 shortcut (GABO_SYMMETRIC): i <= j evaluated, mirrored; not used for `value`"},
-            "parity": {"max_rel_err_vs_oracle_256x256": max_rel, "symmetric": max_rel_sym, "tolerance": 1e-5},
+            "parity": parity, "full": args.full,
         }
         line["expected_scaling"] = {
             "note": "stated BEFORE any multi-GPU hardware run (none was available to the builder): the model a SCALE run is to be judged against",
@@ -923,7 +945,7 @@ def main():
             line["sharded_gram"] = sharded
         if sphere_sweep_result is not None:
             line["acq_sweep_sphere"] = sphere_sweep_result
-        if not args.no_sweep and not args.sweep_lite:
+        if args.full and not args.no_sweep and not args.sweep_lite:
             # config 2 of BASELINE.json beside the headline: SphereGaussianKernel S^9, N=4096 (HBM-write bound: 8.04 B/pair)
             from gabotorch_amd import ops as _ops
             from oracle import sphere as osph
@@ -1047,7 +1069,7 @@ def main():
             line["surrogate_fit"] = {"workload": "fit_gpytorch_model: SingleTaskGP(ScaleKernel(SpdAffineInvariantGaussianKernel)), 50 "
                                                  "observations on S^5_++, Gamma priors, L-BFGS-B (gabo_gp_mll: likelihood + analytic "
                                                  "gradient in one launch per evaluation)", "ms": fit_ms}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, kcpu = cpu_baseline(x)
             cb["max_rel_diff_gpu_vs_cpu_port"] = float(np.max(np.abs(job.out[:kcpu.shape[0]].cpu().numpy() - kcpu) / np.abs(kcpu)))
             line["cpu_baseline"] = cb

@@ -19,7 +19,7 @@ def test_bench_two_ranks_on_one_device(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--preheat", "5",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=1500)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=1500)
     log = os.path.join(ROOT, "gpurun_out")
     os.makedirs(log, exist_ok=True)
     with open(os.path.join(log, "bench_two_ranks_one_device.log"), "w") as f:
@@ -59,7 +59,7 @@ def test_bench_one_rank_through_rccl(tmp_path):
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--preheat", "5", "--no-cpu-baseline", "--no-sweep"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--preheat", "5", "--full", "--no-cpu-baseline", "--no-sweep"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     log = os.path.join(ROOT, "gpurun_out")
     os.makedirs(log, exist_ok=True)
@@ -82,7 +82,7 @@ def test_bench_eight_ranks_on_one_device(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--preheat", "2",
-                        "--no-cpu-baseline", "--no-symmetric", "--sweep-lite"], env=env, capture_output=True, text=True, timeout=1800)
+                        "--full", "--no-cpu-baseline", "--no-symmetric", "--sweep-lite"], env=env, capture_output=True, text=True, timeout=1800)
     log = os.path.join(ROOT, "gpurun_out")
     os.makedirs(log, exist_ok=True)
     with open(os.path.join(log, "bench_eight_ranks_one_device.log"), "w") as f:

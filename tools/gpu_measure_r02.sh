@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r02_measure
 mkdir -p $O
 cd $R
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
 timeout 600 python tools/dim_sweep.py 2>&1 | grep -v amdgpu > $O/dim_sweep.txt
 timeout 600 python tools/tr_latency.py 2>&1 | grep -v amdgpu > $O/tr_latency.txt
 timeout 900 python tools/config5_bench.py 2>&1 | grep -v amdgpu > $O/config5.txt

@@ -4,7 +4,7 @@ O=$R/gpurun_out/r04_refresh
 mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -q 2>&1 | tail -3 | tee $O/gpu_suite.txt
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
 bash tools/collect_profiles_r04.sh > $O/collect.log 2>&1
 timeout 900 python tools/hd_gabo_breakdown.py 2>&1 | grep -v amdgpu > $O/hd_gabo.txt
 timeout 600 python tools/hd_gabo_sphere_breakdown.py 2>&1 | grep -v amdgpu > $O/hd_gabo_sphere.txt
