@@ -25,6 +25,7 @@ GABO_GP_MLL_LARGE_MAX_N = 2048
 GABO_METRIC_AFFINE_INVARIANT, GABO_METRIC_LOG_EUCLIDEAN, GABO_METRIC_FROBENIUS = 0, 8, 16
 GABO_CONSTRAINT_MAX_EIGENVALUE, GABO_CONSTRAINT_MIN_EIGENVALUE = 0, 1
 GABO_CONSTRAINT_MAX_EIGENVALUE_NESTED, GABO_CONSTRAINT_MIN_EIGENVALUE_NESTED = 2, 3
+GABO_TR_SHORTCUT_COUNTERS = 5            # value first, value first then accepted, step reused, fast-forwarded, generic-workspace restarts
 GABO_RECON_AFFINE_INVARIANT, GABO_RECON_LOG_EUCLIDEAN = 0, 1
 GABO_RECON_MAX_LOOKAHEAD = 4
 GABO_RECON_STOP = ("max iterations", "max time", "min step size", "min grad norm")     # GABO_RECON_STOP_* of the header, by code
@@ -149,6 +150,8 @@ SIGNATURES = {
     "gabo_spd_tr_solve_supported": (_I, [_P, _I64, _I, _I, _I]),
     "gabo_spd_tr_two_waves": (_I, [_I]),
     "gabo_spd_tr_two_waves_counters": (_I, [_P, _P, _I]),
+    "gabo_spd_tr_shortcuts": (_I, [_I]),
+    "gabo_spd_tr_shortcut_counters": (_I, [_P]),
     "gabo_spd_tr_propose_supported": (_I, [_I, _I]),
     "gabo_sphere_tr_propose": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _I64, _I, _I, _D, _D, _D, _I, _I, _I, _P, _P]),
     "gabo_sphere_tr_update": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I, _I, _D, _D, _D, _D, _I64, _P, _P]),

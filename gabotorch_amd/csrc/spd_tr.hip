@@ -51,12 +51,20 @@ void tr_record_take(double** buffer, int64_t* capacity) {
     g_tr_record_cap = 0;
 }
 
+// gabo_spd_tr_shortcuts: 0 runs every iteration of the single-launch solves in full (no value-first evaluation after a rejection, no reuse of an identical
+// step's proposal, no fast-forward over runs of rejections), in the one-wave and the two-wave kernel alike; the two forms must agree bit for bit
+// (tests/test_gpu_solve_shortcuts.py).  GABO_TR_NO_SHORTCUTS in the environment sets the initial value, as GABO_TR_DUO does for the two-wave form.
+static int& shortcuts_enabled() {
+    static int enabled = getenv("GABO_TR_NO_SHORTCUTS") ? 0 : 1;
+    return enabled;
+}
+// gabo_spd_tr_shortcut_counters: the caller's device buffer of GABO_TR_SHORTCUT_COUNTERS sums, or null
+static unsigned long long* g_shortcut_counters = nullptr;
+
 int tr_solve_dispatch(const SolveArgs& a0) {
     SolveArgs a = a0;
-    // test hook: GABO_TR_NO_SHORTCUTS in the environment runs every iteration in full (no value-first evaluation after a rejection, no reuse of
-    // an identical step's proposal): the two forms must agree bit for bit (tests/test_gpu_native_sweep.py).  Read once per process.
-    static const int shortcuts = getenv("GABO_TR_NO_SHORTCUTS") ? 0 : 1;
-    a.shortcuts = shortcuts;
+    a.shortcuts = shortcuts_enabled();
+    a.counters = g_shortcut_counters;
     switch (a.P->flags & GABO_METRIC_MASK) {
         case GABO_METRIC_AFFINE_INVARIANT: return solve_affine_invariant(a);
         case GABO_METRIC_LOG_EUCLIDEAN: return solve_log_euclidean(a);
@@ -146,6 +154,17 @@ int gabo_spd_tr_solve_supported(const gabo_spd_acq_params* acq, int64_t r, int d
 #endif
     return gabo::solve_supported(metric == GABO_METRIC_LOG_EUCLIDEAN ? 1 : metric == GABO_METRIC_FROBENIUS ? 2 : 0, acq->n, r, d, n_constraints, has_factors, nested_bytes,
                                  gabo::tr_factor_count(*acq)) ? 1 : 0;
+}
+
+int gabo_spd_tr_shortcuts(int enable) {
+    const int before = gabo::shortcuts_enabled();
+    if (enable == 0 || enable == 1) gabo::shortcuts_enabled() = enable;
+    return before;
+}
+
+int gabo_spd_tr_shortcut_counters(long long* device_buffer) {
+    gabo::g_shortcut_counters = reinterpret_cast<unsigned long long*>(device_buffer);
+    return GABO_OK;
 }
 
 int gabo_tr_solve_record(double* buffer, int64_t max_iterations) {

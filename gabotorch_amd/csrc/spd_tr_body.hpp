@@ -402,7 +402,8 @@ __device__ __forceinline__ int tr_propose_body(const double* __restrict__ x, con
                                                 double delta_cons, double theta, double kappa, int mininner, int maxinner,
                                                 AcqLds<D>& acq, double* mats, double* dyn, int* __restrict__ status,
                                                 const BuiltinCons* builtin, bool x_unchanged = false, bool fd0_kept = false,
-                                                double* nlds = nullptr, bool value_only = false, double* step_cache = nullptr) {
+                                                double* nlds = nullptr, bool value_only = false, double* step_cache = nullptr,
+                                                int* n_reused = nullptr) {
     constexpr int T = tri_size(D);
     const TcgWs& w = t.tcg;
     double* xfd = t.x_fd + i * T;
@@ -433,6 +434,7 @@ __device__ __forceinline__ int tr_propose_body(const double* __restrict__ x, con
         if (!running) break;
     }
     if (tr_build_proposal<D>(t, x_prop, i, x_unchanged, step_cache, mats)) {
+        if (n_reused != nullptr) ++*n_reused;
         GABO_TICK(7);
         GABO_TICK(8);
         return inner;
@@ -626,7 +628,7 @@ static __device__ __forceinline__ TrFirstStep tr_first_step(double Delta, const 
 // radius: config 4 has such restarts reject 98 proposals in a row, 17 k cycles each, and they were the duration of the launch - eta, the proposal, its value,
 // the model decrease and therefore the verdict are those of this iteration again.  What such an iteration does to the state is known - one more count, the
 // radius quartered again (tr_update_body) - and is applied here for as many iterations as the first-step logic (scalars only) returns the same step: bit
-// for bit the state those iterations would have left (tests/test_gpu_native_sweep.py compares with GABO_TR_NO_SHORTCUTS).  Hd: H delta_0~ as tcg_step left it
+// for bit the state those iterations would have left (tests/test_gpu_solve_shortcuts.py compares with gabo_spd_tr_shortcuts(0)).  Hd: H delta_0~ as tcg_step left it
 // (M4 of its LDS tile); the workspace still holds delta_0~, the scalars of tcg_begin and the constraints (tCG's stop path does not touch them).
 // Returns the number of iterations applied; *still becomes false when maxiter is reached.
 #ifdef GABO_TR_FF_INLINE
@@ -780,7 +782,8 @@ __global__ __launch_bounds__(64, GABO_TR_SOLVE_MIN_WAVES) void spd_tr_solve_kern
                                                           double kappa, int mininner, int maxinner, double delta_bar, double rho_prime,
                                                           double rho_regularization, double mingradnorm, int64_t maxiter,
                                                           int* __restrict__ status, int stage_gp, int ws_lds, int nested_off, int shortcuts,
-                                                          double* __restrict__ rec, int64_t rec_cap, TrStart S) {
+                                                          double* __restrict__ rec, int64_t rec_cap, TrStart S,
+                                                          unsigned long long* __restrict__ counters) {      // gabo_spd_tr_shortcut_counters, or null
     static_assert(D <= 8, "built-in constraints use the register eigen-solver");
     constexpr int dd = D * D;
     __shared__ AcqLds<D> acq;
@@ -847,6 +850,7 @@ __global__ __launch_bounds__(64, GABO_TR_SOLVE_MIN_WAVES) void spd_tr_solve_kern
     double* const step_cache = nullptr;
 #endif
     int64_t rec_k = rec != nullptr ? iters[i] : 0;      // gabo_tr_solve_record: index of the outer iteration being recorded
+    int n_lazy = 0, n_lazy_accepted = 0, n_reused = 0, n_skipped = 0;      // this restart's shortcut counts (gabo_spd_tr_shortcut_counters)
     for (;;) {
         // Value first after a rejection.  The restarts that set this launch's duration are the ones whose proposals are rejected again and again
         // (config 4: 4 of 512 restarts sit on the eigenvalue bound and have 99 of their 100 proposals rejected, the radius ending at 2.4e-60, while
@@ -859,9 +863,11 @@ __global__ __launch_bounds__(64, GABO_TR_SOLVE_MIN_WAVES) void spd_tr_solve_kern
 #else
         const bool lazy = cons_fresh && shortcuts != 0;
 #endif
+        n_lazy += lazy ? 1 : 0;
 #ifndef GABO_TR_SINGLE_SITE     /* the iteration as tr_propose_body (two inlined acquisition evaluations) + a third evaluation here */
         last_inner = tr_propose_body<D, METRIC>(x + i * dd, g + i * dd, delta_tr[i], nullptr, nullptr, Ps, t, xp, iw, Rw, C, 0, delta_cons, theta,
-                                                kappa, mininner, maxinner, acq, mats, dyn, status, &B, cons_fresh, last_inner == 1, nlds, lazy, step_cache);
+                                                kappa, mininner, maxinner, acq, mats, dyn, status, &B, cons_fresh, last_inner == 1, nlds, lazy, step_cache,
+                                                &n_reused);
         __syncthreads();
         if (rec != nullptr && rec_k < rec_cap) {          // (the iterate, its radius and the stop reason of the tCG run that made the proposal)
             double* rr = rec + (rec_k * R + i) * (dd + 2);
@@ -874,6 +880,7 @@ __global__ __launch_bounds__(64, GABO_TR_SOLVE_MIN_WAVES) void spd_tr_solve_kern
         ++rec_k;
         const bool inval = (B.strict && C > 0) ? builtin_infeasible<D>(xp, B, nlds) : false;
         if (lazy && tr_would_accept(fx[i], t.fx_prop[iw], t.rhoden[iw], inval, rho_prime, rho_regularization)) {
+            ++n_lazy_accepted;
             acq_eval_any<D, METRIC>(t.xp_mandel + iw * T_, Ps, t.fx_prop + iw, t.eg_prop + iw * T_, t.F + iw * T_ * Ps.n, acq, dyn, status,
                                     iw + t.tcg.index_base);
             __syncthreads();
@@ -914,6 +921,7 @@ __global__ __launch_bounds__(64, GABO_TR_SOLVE_MIN_WAVES) void spd_tr_solve_kern
                     do_eval = !(it == 0 && x_unchanged);
                 } else if (phase == PH_PROP) {
                     do_eval = !tr_build_proposal<D>(t, xp, iw, x_unchanged, step_cache, mats);
+                    n_reused += do_eval ? 0 : 1;
                     GABO_TICK(7);
                     ex = xpm;
                     ev = t.fx_prop + iw;
@@ -945,8 +953,12 @@ __global__ __launch_bounds__(64, GABO_TR_SOLVE_MIN_WAVES) void spd_tr_solve_kern
                     }
                     ++rec_k;
                     inval = (B.strict && C > 0) ? builtin_infeasible<D>(xp, B, nlds) : false;
-                    if (lazy && tr_would_accept(fx[i], t.fx_prop[iw], t.rhoden[iw], inval, rho_prime, rho_regularization)) phase = PH_REGRAD;
-                    else break;
+                    if (lazy && tr_would_accept(fx[i], t.fx_prop[iw], t.rhoden[iw], inval, rho_prime, rho_regularization)) {
+                        ++n_lazy_accepted;
+                        phase = PH_REGRAD;
+                    } else {
+                        break;
+                    }
                 } else {
                     __syncthreads();
                     break;
@@ -962,14 +974,23 @@ __global__ __launch_bounds__(64, GABO_TR_SOLVE_MIN_WAVES) void spd_tr_solve_kern
 #ifndef GABO_TR_NO_FAST_FORWARD
         if (still && !accepted && last_inner == 1 && t.tcg.running[iw] == 0 && shortcuts != 0 && rec == nullptr && rho_prime < 0.25) {
             bool still_ff = true;
-            tr_repeat_rejected(t.tcg, iw, Rw, D, C, mats + 4 * dd, delta_cons, delta_tr + i, iters + i, maxiter, &still_ff);
+            n_skipped += tr_repeat_rejected(t.tcg, iw, Rw, D, C, mats + 4 * dd, delta_cons, delta_tr + i, iters + i, maxiter, &still_ff);
             if (!still_ff) break;
         }
 #endif
         if (!still) break;
         cons_fresh = !accepted;
     }
-    if (threadIdx.x == 0) active[i] = 0;
+    if (threadIdx.x == 0) {
+        active[i] = 0;
+        if (counters != nullptr) {          // (one atomic per counter that moved, per restart)
+            if (n_lazy) atomicAdd(counters + 0, (unsigned long long)n_lazy);
+            if (n_lazy_accepted) atomicAdd(counters + 1, (unsigned long long)n_lazy_accepted);
+            if (n_reused) atomicAdd(counters + 2, (unsigned long long)n_reused);
+            if (n_skipped) atomicAdd(counters + 3, (unsigned long long)n_skipped);
+            if constexpr (!LAT) atomicAdd(counters + 4, 1ull);
+        }
+    }
     if (own_finish) {
         __syncthreads();
         tr_finish_body<D>(S, x + i * dd, fx[i], iters[i]);
@@ -1076,7 +1097,8 @@ struct SolveArgs {
     hipStream_t st;
     double* rec = nullptr;  // gabo_tr_solve_record: per-iteration record of this call, or null
     int64_t rec_cap = 0;
-    int shortcuts = 1;      // 0: every iteration computes its proposal and the full evaluation (the environment variable GABO_TR_NO_SHORTCUTS: tests)
+    int shortcuts = 1;      // 0: every iteration runs in full - no value-first evaluation, no step reuse, no fast-forward (gabo_spd_tr_shortcuts: tests)
+    unsigned long long* counters = nullptr;      // gabo_spd_tr_shortcut_counters: GABO_TR_SHORTCUT_COUNTERS per-launch sums, or null
     TrStart start = {nullptr, 0, nullptr, 0.0, nullptr, nullptr, nullptr, nullptr};      // the sweep driver's start / end inside the launch (spd_sweep.hip)
 };
 
@@ -1116,7 +1138,7 @@ static int dispatch_solve(const SolveArgs& a) {
     hipLaunchKernelGGL((spd_tr_solve_kernel<DD, METRIC, LAT_>), dim3((unsigned)a.r), dim3(64), lds, a.st, a.x, a.fx, a.g, a.ng, a.delta_tr, \
                        a.active, a.iters, *a.P, a.B, a.ws, a.r, a.delta_cons, a.theta, a.kappa, a.mininner, a.maxinner, a.delta_bar, \
                        a.rho_prime, a.rho_regularization, a.mingradnorm, a.maxiter, a.status, stage_gp, ws_lds, nested_off, a.shortcuts, a.rec, a.rec_cap, \
-                       a.start)
+                       a.start, a.counters)
 #define GABO_CASE(DD)                                                                                                              \
     case DD:                                                                                                                       \
         if constexpr (DD >= DMIN && DD <= DMAX) {                                                                                  \

@@ -236,7 +236,8 @@ __global__ __launch_bounds__(128) void spd_tr_solve_duo_kernel(double* __restric
                                                                int mininner, int maxinner, double delta_bar, double rho_prime,
                                                                double rho_regularization, double mingradnorm, int64_t maxiter,
                                                                int* __restrict__ status, int shortcuts, double* __restrict__ rec, int64_t rec_cap,
-                                                               TrStart S, int* __restrict__ counters) {      // counters: {hits, misses} or null
+                                                               TrStart S, int* __restrict__ counters,      // counters: {hits, misses} or null
+                                                               unsigned long long* __restrict__ sc_counters) {      // gabo_spd_tr_shortcut_counters, or null
     static_assert(D <= 8, "register eigen-solvers");
     constexpr int dd = D * D;
     constexpr int T = tri_size(D);
@@ -289,6 +290,7 @@ __global__ __launch_bounds__(128) void spd_tr_solve_duo_kernel(double* __restric
     const double* xi = x + i * dd;
     duo_block_sync();
     int n_hit = 0, n_miss = 0, n_skip = 0;
+    int n_lazy = 0, n_lazy_accepted = 0, n_reused = 0;          // shortcut counts: value first (tCG wave), step reuse (proposal wave)
     // Barrier sequence of BOTH waves, per iteration: B1, B2, [B4 after a miss], [B5 when a value-only evaluation is followed by the gradient]; every
     // bracket is decided from words the previous barrier ordered.  The iteration of the tCG wave ends with the update and runs straight into the next
     // begin; the proposal wave spends that time on the eigen-pairs of the proposal it expects to be accepted (the next iterate's constraints).
@@ -300,6 +302,7 @@ __global__ __launch_bounds__(128) void spd_tr_solve_duo_kernel(double* __restric
         for (;;) {
             const bool lazy = x_unchanged && shortcuts != 0;
             const bool fd0_kept = last_inner == 1;
+            n_lazy += lazy ? 1 : 0;
             const double fx_now = fx[i];
             GABO_TICK(20);
             tr_begin_part<D>(xi, g + i * dd, delta_tr[i], nullptr, nullptr, t, 0, 1, C, mats, status, nullptr, x_unchanged, nullptr);
@@ -415,6 +418,7 @@ __global__ __launch_bounds__(128) void spd_tr_solve_duo_kernel(double* __restric
             const bool accept_pred = tr_would_accept(fx_now, t.fx_prop[0], t.rhoden[0], inval, rho_prime, rho_regularization);
             if (lazy && accept_pred) duo_block_sync();                  // B5
 #endif
+            n_lazy_accepted += (lazy && accept_pred) ? 1 : 0;
             bool accepted = false;
             bool still = tr_update_body(x + i * dd, fx + i, g + i * dd, ng + i, delta_tr + i, iters + i, inval, xp, t, 0, D, C, delta_bar,
                                         rho_prime, rho_regularization, mingradnorm, maxiter, mats, &accepted);
@@ -490,6 +494,7 @@ __global__ __launch_bounds__(128) void spd_tr_solve_duo_kernel(double* __restric
                 if (phase != PH_REGRAD) {
                     const double* src = phase == PH_SPEC ? sh.spec_eta[1] : w.eta_w;
                     do_eval = !duo_same_step<D>(src, step_cache, x_unchanged);
+                    n_reused += do_eval ? 0 : 1;
                     if (do_eval) duo_proposal_from_eta<D>(w.chol, src, xp, xpm, mats);
                     gout = lazy ? nullptr : t.eg_prop;
                     GABO_TICK(34);
@@ -554,7 +559,10 @@ __global__ __launch_bounds__(128) void spd_tr_solve_duo_kernel(double* __restric
             }
         }
     }
-    if (wv != 0) return;
+    if (wv != 0) {
+        if (lane == 0 && sc_counters != nullptr && n_reused) atomicAdd(sc_counters + 2, (unsigned long long)n_reused);
+        return;
+    }
 #ifdef GABO_DUO_TIMES
     if (lane == 0 && i < 1024) {
         g_duo_times[4 * i] = (long long)__builtin_amdgcn_s_memtime() - t_start;
@@ -568,6 +576,11 @@ __global__ __launch_bounds__(128) void spd_tr_solve_duo_kernel(double* __restric
         if (counters != nullptr) {
             atomicAdd(counters, n_hit);
             atomicAdd(counters + 1, n_miss);
+        }
+        if (sc_counters != nullptr) {
+            if (n_lazy) atomicAdd(sc_counters + 0, (unsigned long long)n_lazy);
+            if (n_lazy_accepted) atomicAdd(sc_counters + 1, (unsigned long long)n_lazy_accepted);
+            if (n_skip) atomicAdd(sc_counters + 3, (unsigned long long)n_skip);
         }
     }
     if (own_finish) {

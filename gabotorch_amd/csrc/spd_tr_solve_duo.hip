@@ -89,7 +89,7 @@ static int launch_duo(const SolveArgs& a) {
     const size_t lds = duo_lds_layout(a.P->n, D, a.B.n).bytes;
     hipLaunchKernelGGL((spd_tr_solve_duo_kernel<D>), dim3((unsigned)a.r), dim3(64, 2), lds, a.st, a.x, a.fx, a.g, a.ng, a.delta_tr, a.active, a.iters,
                        *a.P, a.B, a.r, a.delta_cons, a.theta, a.kappa, a.mininner, a.maxinner, a.delta_bar, a.rho_prime, a.rho_regularization,
-                       a.mingradnorm, a.maxiter, a.status, a.shortcuts, a.rec, a.rec_cap, a.start, counters);
+                       a.mingradnorm, a.maxiter, a.status, a.shortcuts, a.rec, a.rec_cap, a.start, counters, a.counters);
     return hipGetLastError() == hipSuccess ? GABO_OK : GABO_ERR_LAUNCH;
 }
 

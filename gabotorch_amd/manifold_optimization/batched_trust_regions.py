@@ -521,7 +521,7 @@ class BatchedTrustRegions:
             active = active & ~stop
             if not bool(active.any()) or (time.time() - time0) >= self.maxtime:
                 break
-        self.log = {"iterations": k, "per_restart_iterations": iters, "final_cost": fx, "final_gradnorm": ng,
+        self.log = {"iterations": k, "per_restart_iterations": iters, "final_cost": fx, "final_gradnorm": ng, "final_radius": Delta,
                     "cost_evals": problem.n_cost, "grad_evals": problem.n_grad, "time": time.time() - time0}
         return x
 
@@ -713,7 +713,7 @@ class BatchedTrustRegions:
                                            "stop_inner": torch.where(ran, rec[kk, :, L + 1], torch.full_like(rec[kk, :, L], -1.0)).long()})
                 ops.check_deferred()
                 self.log = {"iterations": k, "per_restart_iterations": S.iters, "final_cost": S.fx, "final_gradnorm": S.ng,
-                            "cost_evals": problem.n_cost, "grad_evals": problem.n_grad, "time": time.time() - time0, "one_launch_solve": True}
+                            "final_radius": S.Delta, "cost_evals": problem.n_cost, "grad_evals": problem.n_grad, "time": time.time() - time0, "one_launch_solve": True}
                 return S.x
 
         # Execution plan.  Eager: the parts in order, with the inner loop leaving as soon as no restart runs.  hipGraphs: the
@@ -770,7 +770,7 @@ class BatchedTrustRegions:
         finally:
             if prev_check is not None:
                 ops.set_error_checking(prev_check)
-        self.log = {"iterations": k, "per_restart_iterations": S.iters, "final_cost": S.fx, "final_gradnorm": S.ng,
+        self.log = {"iterations": k, "per_restart_iterations": S.iters, "final_cost": S.fx, "final_gradnorm": S.ng, "final_radius": S.Delta,
                     "cost_evals": problem.n_cost, "grad_evals": problem.n_grad, "time": time.time() - time0}
         return S.x
 

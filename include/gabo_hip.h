@@ -491,6 +491,20 @@ int gabo_spd_tr_solve_supported(const gabo_spd_acq_params* acq, int64_t r, int d
  * truncated CG leaving with the speculated step (hits) and how many did not (misses: the proposal was evaluated again, the one-wave schedule). */
 int gabo_spd_tr_two_waves(int enable);
 int gabo_spd_tr_two_waves_counters(long long* hits, long long* misses, int reset);
+/* The shortcuts of the single launch (one wave and two waves per restart alike; csrc/spd_tr_body.hpp): after a rejected proposal the next one's value is
+ * evaluated first and its gradient only if it is accepted; a proposal built from the same step as the previous one at the same iterate is reused; a run of
+ * rejected proposals whose first truncated-CG step does not change is applied as scalar updates (one more iteration, the radius quartered).  Each leaves
+ * every bit of the result as the full iterations would.  gabo_spd_tr_shortcuts(0 / 1) turns them off / on for this process and returns the previous
+ * setting (-1: only query; initially on unless GABO_TR_NO_SHORTCUTS is in the environment).  gabo_spd_tr_shortcut_counters registers a device buffer of
+ * GABO_TR_SHORTCUT_COUNTERS long longs (NULL withdraws it) to which every later single-launch solve of this process adds, per restart, at its end: */
+#define GABO_TR_SHORTCUT_COUNTERS 5
+#define GABO_TR_SC_VALUE_FIRST 0              /* iterations whose proposal was evaluated value first */
+#define GABO_TR_SC_VALUE_FIRST_ACCEPTED 1     /* ... of which accepted: the gradient was evaluated afterwards */
+#define GABO_TR_SC_STEP_REUSED 2              /* proposals reused because the step had not changed */
+#define GABO_TR_SC_FAST_FORWARDED 3           /* rejected iterations applied as scalar updates */
+#define GABO_TR_SC_GENERIC_WORKSPACE 4        /* restarts run by the generic-workspace form of the one-wave kernel (not a shortcut) */
+int gabo_spd_tr_shortcuts(int enable);
+int gabo_spd_tr_shortcut_counters(long long* device_buffer);
 
 /* ------------------------------------------------------------------------------------------------------------
  * One multi-start acquisition sweep on S^d_++ through a native host driver: the device work of

@@ -12,6 +12,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from gabotorch_amd import _lib
+
 pytestmark = pytest.mark.gpu
 
 
@@ -57,23 +59,31 @@ def test_native_sweep_declines_what_it_does_not_cover():
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(strict=True), dict(constraint=False), dict(maxiter=250)])
-def test_one_launch_solve_shortcuts_do_not_change_a_bit(kw, monkeypatch):
-    """The single-launch solve evaluates a proposal's value before its gradient after a rejection and reuses the previous proposal when tCG returns
-    the same step again (csrc/spd_tr_body.hpp).  With GABO_TR_NO_SHORTCUTS in the environment the same kernel runs every iteration in full (the form of
-    rounds 1-4): final iterates, costs and iteration counts of all 512 restarts must agree bit for bit - including the restarts that sit on the
-    eigenvalue bound and have every proposal but one rejected (radius down to 1e-150 at 250 iterations)."""
+def test_one_launch_solve_shortcuts_do_not_change_a_bit(kw):
+    """The single-launch solve evaluates a proposal's value before its gradient after a rejection, reuses the previous proposal when tCG returns
+    the same step again and applies runs of rejected proposals with the same first step as scalar updates (csrc/spd_tr_body.hpp).  With
+    gabo_spd_tr_shortcuts(0) the same kernel runs every iteration in full (the form of rounds 1-4): final iterates, costs, radii and iteration counts
+    of all 512 restarts must agree bit for bit - including the restarts that sit on the eigenvalue bound and have every proposal but one rejected
+    (radius down to 1e-150 at 250 iterations).  The shortcut counters (gabo_spd_tr_shortcut_counters) prove which form ran."""
+    from tests.test_gpu_solve_shortcuts import FAST_FORWARDED, SHORTCUT_SLOTS, new_counters, switches
     from tools.sweep_bench import run_sweep
-    monkeypatch.delenv("GABO_TR_NO_SHORTCUTS", raising=False)
-    _, b1, v1, l1 = run_sweep("cuda:0", device_rand=True, builtin_constraint=True, native_sweep=False, **kw)
-    monkeypatch.setenv("GABO_TR_NO_SHORTCUTS", "1")
-    _, b2, v2, l2 = run_sweep("cuda:0", device_rand=True, builtin_constraint=True, native_sweep=False, **kw)
-    monkeypatch.delenv("GABO_TR_NO_SHORTCUTS")
+    counters = new_counters()
+    runs = []
+    for shortcuts in (True, False):
+        with switches(shortcuts, _lib.load().gabo_spd_tr_two_waves(-1), counters):
+            _, b, v, log = run_sweep("cuda:0", device_rand=True, builtin_constraint=True, native_sweep=False, **kw)
+            runs.append((b, v, log, counters.cpu().tolist()))
+    (b1, v1, l1, c1), (b2, v2, l2, c2) = runs
     assert l1.get("one_launch_solve") and l2.get("one_launch_solve")
     assert torch.equal(l1["per_restart_iterations"].cpu(), l2["per_restart_iterations"].cpu())
     np.testing.assert_array_equal(l1["final_cost"].cpu().numpy(), l2["final_cost"].cpu().numpy())
+    np.testing.assert_array_equal(l1["final_radius"].cpu().numpy(), l2["final_radius"].cpu().numpy())
+    np.testing.assert_array_equal(l1["final_gradnorm"].cpu().numpy(), l2["final_gradnorm"].cpu().numpy())
     assert torch.equal(b1, b2) and v1 == v2
+    assert sum(c1[s] for s in SHORTCUT_SLOTS) > 0 and [c2[s] for s in SHORTCUT_SLOTS] == [0] * 4, (c1, c2)
     if kw.get("constraint", True) and not kw.get("strict"):
         assert int(l1["per_restart_iterations"].max()) == kw.get("maxiter", 100)       # (the restarts on the bound are in the set)
+        assert c1[FAST_FORWARDED] > 0, c1
 
 
 def test_native_sweep_on_the_log_euclidean_surrogate_of_config_5():

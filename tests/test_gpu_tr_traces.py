@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from gabotorch_amd import manifolds, models, ops
+from gabotorch_amd import _lib, manifolds, models, ops
 from gabotorch_amd.kernel_utils.kernels_spd import SpdAffineInvariantGaussianKernel
 from gabotorch_amd.manifold_optimization.batched_trust_regions import BatchedProblem
 from gabotorch_amd.manifold_optimization.constrained_trust_regions import ConstrainedTrustRegions, StrictConstrainedTrustRegions
@@ -152,7 +152,7 @@ def test_device_resident_plans_reach_the_reference_fp64_optima(golden, name):
         ops.set_error_checking(True)
 
 
-@pytest.mark.parametrize("plan", ["tcg_launches", "propose_update_launches", "single_launch_solve"])
+@pytest.mark.parametrize("plan", ["tcg_launches", "propose_update_launches", "single_launch_solve", "single_launch_solve_no_shortcuts"])
 @pytest.mark.parametrize("name,run", [("spd3", "tr_fd"), ("spd5", "tr_fd"), ("spd2", "tr_fd"), ("spd3", "con"), ("spd5c", "con"),
                                       ("spd3", "strict"), ("spd5c", "strict")])
 def test_device_plans_follow_the_reference_trace(golden, name, run, plan):
@@ -161,8 +161,10 @@ def test_device_plans_follow_the_reference_trace(golden, name, run, plan):
     than the reference's numpy) - walked against the REFERENCE solver's own fp64 record iteration by iteration: radius (exact), tCG stop
     reason, iterate within 1e-6, like the generic path above - and the single-launch solve (gabo_spd_tr_solve with the eigenvalue bound
     built by functools.partial as in examples/gabo_spd.py:136-138, evaluated inside the kernel), which writes its own record
-    (gabo_tr_solve_record).  Round 5: the kernels' finite-difference step had been 2^-13 instead of approximate_hessian.py:40's 2^-14 -
-    1e-4 of H delta, enough to reach the same optima by other iterates."""
+    (gabo_tr_solve_record) - with its shortcuts on and, "no_shortcuts", off (gabo_spd_tr_shortcuts(0): no value-first evaluation, no step reuse; a
+    recording solve never fast-forwards, see test_single_launch_fast_forward_ends_where_the_recorded_run_ends).  Round 5: the kernels' finite-difference
+    step had been 2^-13 instead of approximate_hessian.py:40's 2^-14 - 1e-4 of H delta, enough to reach the same optima by other iterates."""
+    from tests.test_gpu_solve_shortcuts import switches
     g = golden("tr_traces.npz")
     d = int(name.rstrip("c")[3:])
     Y = ospd.symmetric_matrix_to_vector_mandel(g[f"{name}_Y"])
@@ -181,17 +183,20 @@ def test_device_plans_follow_the_reference_trace(golden, name, run, plan):
     else:
         solver = (ConstrainedTrustRegions if constrained else TrustRegions)(mingradnorm=1e-4, maxiter=100)
     solver.trace = []
-    if plan == "single_launch_solve":
+    one_launch = plan.startswith("single_launch_solve")
+    if one_launch:
         cons = [functools.partial(scut.max_eigenvalue_constraint_torch, maximum_eigenvalue=mx)] if constrained else None
     else:
         cons = [lambda m: scut.max_eigenvalue_constraint_torch(m, mx)] if constrained else None
-    options = {"tcg_launches": {"device_iteration": False}, "propose_update_launches": {"device_solve": False}, "single_launch_solve": {}}[plan]
+    options = {"tcg_launches": {"device_iteration": False}, "propose_update_launches": {"device_solve": False}}.get(plan, {})
+    lib = _lib.load()
     ops.set_error_checking(False)
     try:
-        gen_candidates_manifold(x0, acq, man, solver, pre, post, inequality_constraints=cons, approx_hessian=True, options=options)
+        with switches(plan != "single_launch_solve_no_shortcuts", lib.gabo_spd_tr_two_waves(-1)):
+            gen_candidates_manifold(x0, acq, man, solver, pre, post, inequality_constraints=cons, approx_hessian=True, options=options)
     finally:
         ops.set_error_checking(True)
-    assert solver.trace and ("one_launch_solve" in solver.log) == (plan == "single_launch_solve")
+    assert solver.trace and ("one_launch_solve" in solver.log) == one_launch
     assert ("eta" in solver.trace[0]) == (plan == "tcg_launches")                      # (which plan recorded it)
     ok = g[f"{name}_{run}_f64_ok"]
     res = compare_with_reference_trace(solver.trace, g, f"{name}_{run}_f64", atol_x=1e-6)
@@ -199,6 +204,58 @@ def test_device_plans_follow_the_reference_trace(golden, name, run, plan):
     whole = [agree == nit or (run == "strict" and agree >= 30 and drift < 1e-6) for s, (agree, nit, worst, parted_at, drift) in enumerate(res) if ok[s]]
     print(name, run, plan, "restarts followed to the end:", sum(whole), "of", len(whole), [r[:2] for s, r in enumerate(res) if ok[s] and r[0] != r[1]])
     assert all(whole), [(s,) + r for s, r in enumerate(res) if ok[s] and r[0] != r[1]]
+
+
+@pytest.mark.parametrize("name,run", [("spd3", "con"), ("spd5c", "con"), ("spd3", "strict"), ("spd5c", "strict")])
+def test_single_launch_fast_forward_ends_where_the_recorded_run_ends(golden, name, run):
+    """A solve that writes its record (gabo_tr_solve_record) runs every rejected iteration; one that does not applies runs of rejections with an
+    unchanged first tCG step as scalar updates (tr_repeat_rejected: one more iteration, the radius quartered).  The restarts of these runs reject
+    4-97 proposals in a row down to radii of 1e-58.  The recorded run follows the reference's fp64 record iteration by iteration, radius exact
+    (test_device_plans_follow_the_reference_trace); the run without the record must end in its state bit for bit - iterate, cost, gradient norm,
+    radius, iteration count - with the fast-forward shown to have run, and on the reference's iteration counts exactly."""
+    from tests.test_gpu_solve_shortcuts import FAST_FORWARDED, new_counters, switches
+    g = golden("tr_traces.npz")
+    d = int(name.rstrip("c")[3:])
+    Y = ospd.symmetric_matrix_to_vector_mandel(g[f"{name}_Y"])
+    w, beta, mx = g[f"{name}_w"], float(g[f"{name}_beta"]), float(g[f"{name}_maxeig"])
+    kern = SpdAffineInvariantGaussianKernel(beta_min=0.1).double()
+    kern.beta = torch.tensor(beta, dtype=torch.float64)
+    gp = models.ExactGP(t(Y), t(np.zeros(len(w))), kern, outputscale=1.0, noise=1.0, mean=0.0)
+    gp._cache = (torch.eye(len(w), dtype=torch.float64, device=DEV), t(w))          # posterior mean = sum_j w_j k(x, Y_j)
+    acq = models.PosteriorMean(gp, maximize=True)
+    man = manifolds.PositiveDefinite(d)
+    x0 = ops.matrix_to_mandel(t(g[f"{name}_x0"]))[:, None]
+    cons = [functools.partial(scut.max_eigenvalue_constraint_torch, maximum_eigenvalue=mx)]
+    lib = _lib.load()
+    counters = new_counters()
+    out = []
+    for recorded in (True, False):
+        if run == "strict":
+            solver = StrictConstrainedTrustRegions(mingradnorm=2e-4, maxiter=100, minstepsize=1e-4)
+        else:
+            solver = ConstrainedTrustRegions(mingradnorm=1e-4, maxiter=100)
+        if recorded:
+            solver.trace = []
+        ops.set_error_checking(False)
+        try:
+            with switches(True, lib.gabo_spd_tr_two_waves(-1), counters):
+                c, v = gen_candidates_manifold(x0, acq, man, solver, vector_to_symmetric_matrix_mandel_torch, symmetric_matrix_to_vector_mandel_torch,
+                                               inequality_constraints=cons, approx_hessian=True)
+                cnt = counters.cpu().tolist()
+        finally:
+            ops.set_error_checking(True)
+        assert solver.log.get("one_launch_solve")
+        log = solver.log
+        out.append(({"x": c.cpu().numpy(), "value": v.cpu().numpy(), "final_cost": log["final_cost"].cpu().numpy(),
+                     "final_gradnorm": log["final_gradnorm"].cpu().numpy(), "final_radius": log["final_radius"].cpu().numpy(),
+                     "per_restart_iterations": log["per_restart_iterations"].cpu().numpy()}, cnt, solver.trace))
+    (rec, c_rec, trace), (ff, c_ff, _) = out
+    print(name, run, "recorded", c_rec, "not recorded", c_ff, "radii", ff["final_radius"])
+    assert trace and c_rec[FAST_FORWARDED] == 0 and c_ff[FAST_FORWARDED] > 0, (c_rec, c_ff)
+    for k in rec:
+        np.testing.assert_array_equal(ff[k], rec[k], err_msg=k)
+    ok = g[f"{name}_{run}_f64_ok"]
+    np.testing.assert_array_equal(ff["per_restart_iterations"][ok], g[f"{name}_{run}_f64_nit"][ok])
 
 
 @pytest.mark.parametrize("name,run,kw", [("sph5", "tr_exact", {}), ("sph5", "tr_fd", {}), ("sph3", "tr_exact", {}), ("sph3", "tr_fd", {}),

@@ -50,12 +50,24 @@ def _solve(acq, x0, d, cons, strict, maxiter):
     c, v = gen_candidates_manifold(x0, acq, manifolds.PositiveDefinite(d), solver, vector_to_symmetric_matrix_mandel_torch,
                                    symmetric_matrix_to_vector_mandel_torch, inequality_constraints=cons, approx_hessian=True, options={})
     assert "one_launch_solve" in solver.log
-    return c.cpu().numpy(), v.cpu().numpy(), solver.log["per_restart_iterations"].cpu().numpy()
+    return (c.cpu().numpy(), v.cpu().numpy(), solver.log["per_restart_iterations"].cpu().numpy(), solver.log["final_radius"].cpu().numpy(),
+            solver.log["final_gradnorm"].cpu().numpy())
 
 
 @pytest.mark.parametrize("case", ["unconstrained", "max_eig", "box", "box_strict"])
 @pytest.mark.parametrize("d", [2, 3, 4, 5, 6])
 def test_two_waves_match_one_wave_bit_for_bit(d, case):
+    _two_waves_against_one_wave(d, case, shortcuts=1)
+
+
+@pytest.mark.parametrize("case", ["unconstrained", "max_eig", "box", "box_strict"])
+@pytest.mark.parametrize("d", [2, 3, 4, 5, 6])
+def test_two_waves_match_one_wave_bit_for_bit_without_shortcuts(d, case):
+    """the same with gabo_spd_tr_shortcuts(0): the two-wave kernel has its own copy of the shortcuts, and both sides share tr_repeat_rejected"""
+    _two_waves_against_one_wave(d, case, shortcuts=0)
+
+
+def _two_waves_against_one_wave(d, case, shortcuts):
     lib = _lib.load()
     acq, x0 = _problem(d, n_train=20 if d < 6 else 14, seed=300 + d, R=48)
     cons = None
@@ -65,6 +77,9 @@ def test_two_waves_match_one_wave_bit_for_bit(d, case):
             cons.append(functools.partial(scut.min_eigenvalue_constraint_torch, minimum_eigenvalue=0.35))
     strict = case.endswith("strict")
     before = lib.gabo_spd_tr_two_waves(-1)
+    before_sc = lib.gabo_spd_tr_shortcuts(shortcuts)
+    sc = torch.zeros(_lib.GABO_TR_SHORTCUT_COUNTERS, dtype=torch.int64, device=DEV)
+    lib.gabo_spd_tr_shortcut_counters(ctypes.c_void_p(sc.data_ptr()))
     ops.set_error_checking(False)
     try:
         lib.gabo_spd_tr_two_waves(1)
@@ -74,11 +89,16 @@ def test_two_waves_match_one_wave_bit_for_bit(d, case):
         lib.gabo_spd_tr_two_waves(0)
         one = _solve(acq, x0, d, cons, strict, maxiter=25)
         assert _counters(lib, reset=True) == (0, 0)
+        torch.cuda.synchronize()
     finally:
+        lib.gabo_spd_tr_shortcut_counters(None)
         lib.gabo_spd_tr_two_waves(before)
+        lib.gabo_spd_tr_shortcuts(before_sc)
         ops.set_error_checking(True)
     assert hits + misses >= int(two[2].sum()) > 0 or hits + misses > 0          # the two-wave kernel ran (iterations applied as scalar updates are not counted)
     assert hits > 0
+    if not shortcuts:
+        assert sc[:4].tolist() == [0, 0, 0, 0], sc.tolist()          # (slots 0-3 of gabo_spd_tr_shortcut_counters: no shortcut ran on either side)
     for a, b in zip(two, one):
         np.testing.assert_array_equal(a, b)
 
