@@ -111,7 +111,7 @@ __device__ __forceinline__ double sqrt_nz_cubic(double x) {
 // row of 16 lanes are DPP moves on the vector pipe (quad_perm xor 1, xor 2, row_half_mirror, row_mirror: each pairs lanes symmetrically, so
 // all 16 lanes of a row end with the same bits), the rows are combined with row_bcast15 / row_bcast31 (rows 1 and 3 += their lower
 // neighbour, then row 3 += row 1: lane 63 holds (r3 + r2) + (r1 + r0)) and lane 63 is broadcast through two v_readlane: ~21 instructions,
-// no LDS.  All 64 lanes must be active.  GABO_WAVE_SUM_SHFL: the butterfly (A/B).
+// no LDS.  All 64 lanes must be active.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_fetch(double v) {
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
@@ -119,10 +119,6 @@ __device__ __forceinline__ double dpp_fetch(double v) {
     return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ double wave_allsum(double v) {
-#ifdef GABO_WAVE_SUM_SHFL
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-#else
     v += dpp_fetch<0xB1, 0xf>(v);        // quad_perm [1,0,3,2]
     v += dpp_fetch<0x4E, 0xf>(v);        // quad_perm [2,3,0,1]
     v += dpp_fetch<0x141, 0xf>(v);       // row_half_mirror
@@ -130,7 +126,6 @@ __device__ __forceinline__ double wave_allsum(double v) {
     v += dpp_fetch<0x142, 0xa>(v);       // row_bcast15 into rows 1 and 3 (the other rows add the `old` operand: +0.0)
     v += dpp_fetch<0x143, 0xc>(v);       // row_bcast31 into rows 2 and 3
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-#endif
 }
 
 // 1/sqrt(x), x > 0: e = 1 - x y0^2 (|e| <= 2^-23); y0 (1 + e/2 + 3e^2/8) leaves an e^3 error.
@@ -149,14 +144,6 @@ __device__ __forceinline__ double sqrt_pos(double x) {
 
 __device__ __forceinline__ double copysign_d(double mag, double sgn) { return __builtin_copysign(mag, sgn); }
 
-// a * b + c with the addend read from an SGPR pair (c wave-uniform).  hipcc would pick the two-address v_fmac_f64 and
-// first copy the coefficient into the accumulator with two v_mov_b32; VOP3 v_fma_f64 takes the scalar addend directly.
-__device__ __forceinline__ double fma_s(double a, double b, double c_uniform) {
-    double d;
-    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(c_uniform));
-    return d;
-}
-
 // Polynomial coefficients of acos_fast / exp_neg.  fp64 literals cannot be VALU inline operands and hipcc re-materialises
 // each one with two v_mov_b32 in front of every v_fmac (tripling the VALU cost of a Horner step).  A kernel therefore
 // loads the table ONCE into registers (`MathRegs::load()`, laundered through an empty asm so the values are opaque and
@@ -167,19 +154,11 @@ struct MathRegs {
     double log2e, ln2_hi, ln2_lo;
     double inv_fact[12];           // 1/13!, 1/12!, ..., 1/2!
 
-#ifdef GABO_MATH_SGPR   /* coefficients pinned in SGPRs (kernels with spare scalar registers): frees 56 VGPRs */
-    __device__ __forceinline__ static double pin(double v) {
-        asm volatile("" : "+s"(v));
-        return v;
-    }
-    __device__ __forceinline__ static double fmac(double a, double b, double c) { return fma_s(a, b, c); }
-#else
     __device__ __forceinline__ static double pin(double v) {
         asm volatile("" : "+v"(v));
         return v;
     }
     __device__ __forceinline__ static double fmac(double a, double b, double c) { return __builtin_fma(a, b, c); }
-#endif
     __device__ __forceinline__ static MathRegs load() {
         MathRegs t;
         const double pS[6] = {1.66666666666666657415e-01, -3.25565818622400915405e-01, 2.01212532134862925881e-01,

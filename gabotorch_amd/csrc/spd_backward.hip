@@ -19,14 +19,10 @@
 // backward, ms, Jacobi -> QL: d = 8: 39.7 -> see DESIGN.md, d = 10: 70 -> 8.8, d = 12: 228 -> 23.
 #include "gabo_device.hpp"
 #include "spd_prep.hpp"
-#include "spd_jacobi.hpp"
 #include "spd_eigvec.hpp"
 #include "spd_generic.hpp"
 #include "../../include/gabo_hip.h"
 
-#ifndef GABO_BWD_JACOBI_MAX_DIM
-#define GABO_BWD_JACOBI_MAX_DIM 0   /* dimensions up to this use the cyclic Jacobi (A/B builds); the QL solver is faster from d = 3 on */
-#endif
 #ifndef GABO_BWD_TWO_WAVE_MAX_DIM
 #define GABO_BWD_TWO_WAVE_MAX_DIM 8  /* Z + M fit 256 VGPRs up to here: two waves per SIMD */
 #endif
@@ -81,16 +77,12 @@ __global__ __launch_bounds__(64, (D > GABO_BWD_TWO_WAVE_MAX_DIM ? 1 : 2)) void s
             });
         });
         // eigen-decomposition in registers: Householder + QL with vectors (spd_eigvec.hpp)
-        constexpr bool kJacobi = D <= GABO_BWD_JACOBI_MAX_DIM;
         double vreg[D * D];
         double lam[D];
-        if constexpr (kJacobi) {
-            jacobi_eig_reg<D>(m, vreg);
-            static_for<D>([&](auto kk) { lam[decltype(kk)::value] = m[tri(decltype(kk)::value, decltype(kk)::value)]; });
-        } else {
+        {
             // (threshold |e| <= 1e-13 (|d| + |d'|) instead of machine epsilon: logm(M) moves by e f[l_k, l_k+1] <= 1e-13 |log'|, three orders below what a
             // gradient is compared at - and the last sweep of some stages is saved: N = 4096, d = 10 same-box 9.24 -> 9.00 ms, max error / max |grad| against the
-            // oracle 3e-15 -> 5e-14 (1e-22: 8.78 ms, 3e-12; tools/ab_bwd_eps_r05.sh); the trust-region kernels keep the strict form, their traces are pinned)
+            // oracle 3e-15 -> 5e-14 (1e-22: 8.78 ms, 3e-12; round 5); the trust-region kernels keep the strict form, their traces are pinned)
 #ifndef GABO_BWD_QL_EPS2
 #define GABO_BWD_QL_EPS2 1e-26
 #endif
@@ -107,13 +99,6 @@ __global__ __launch_bounds__(64, (D > GABO_BWD_TWO_WAVE_MAX_DIM ? 1 : 2)) void s
         auto Vat = [&](int r, int c) -> double { return vreg[r * D + c]; };
         double lg[D];
         double s = 0.0;
-#ifdef GABO_BWD_OCML_LOG       /* A/B: OCML's log (98 instructions, double-double) as in rounds 1-4 */
-        static_for<D>([&](auto kk) {
-            constexpr int k = decltype(kk)::value;
-            lg[k] = log(lam[k]);
-            s = __builtin_fma(lg[k], lg[k], s);
-        });
-#else
         {
             // the fdlibm-scheme log of the acquisition kernels (gabo_device.hpp: ~35 instructions at 1 ulp) instead of OCML's 98: D of them per pair.
             // An eigenvalue that is not positive (M = C C^T is positive semi-definite by construction: rounding of a singular pair, or NaN factors of
@@ -126,7 +111,6 @@ __global__ __launch_bounds__(64, (D > GABO_BWD_TWO_WAVE_MAX_DIM ? 1 : 2)) void s
                 s = __builtin_fma(lg[k], lg[k], s);
             });
         }
-#endif
         // w = dLoss/d(d^2)
         double d2 = s + 1e-15;
         double go = live ? gout[b * go_sb + i * go_si + j * go_sj] : 0.0;

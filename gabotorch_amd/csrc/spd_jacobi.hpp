@@ -1,5 +1,5 @@
 // Per-lane cyclic Jacobi eigen-decomposition (eigenvalues AND eigenvectors) of a small symmetric matrix held in registers:
-// shared by the SPD backward kernel (spd_backward.hip) and the fused acquisition kernel (spd_acq.hip).
+// the fused acquisition kernel (spd_acq.hip) above d = 8.
 #pragma once
 #include "gabo_device.hpp"
 
@@ -63,12 +63,6 @@ __device__ __forceinline__ void jacobi_eig_acc(double (&m)[tri_size(D)], VAcc&& 
 template <int D>
 __device__ __forceinline__ void jacobi_eig(double (&m)[tri_size(D)], double* __restrict__ vl) {
     jacobi_eig_acc<D>(m, [&](int r, int c) -> double& { return vl[(r * D + c) * 64]; });
-}
-
-// eigenvectors in registers (latency-bound callers with few waves per SIMD and D small enough: D*D + D(D+1)/2 doubles live)
-template <int D>
-__device__ __forceinline__ void jacobi_eig_reg(double (&m)[tri_size(D)], double (&v)[D * D]) {
-    jacobi_eig_acc<D>(m, [&](int r, int c) -> double& { return v[r * D + c]; });
 }
 
 }  // namespace gabo

@@ -147,11 +147,7 @@ int gabo_spd_tr_solve_supported(const gabo_spd_acq_params* acq, int64_t r, int d
     if (metric != GABO_METRIC_AFFINE_INVARIANT && metric != GABO_METRIC_LOG_EUCLIDEAN && metric != GABO_METRIC_FROBENIUS) return 0;
     if (acq->n < 1 || acq->n > gabo_spd_acq_max_train(d)) return 0;
     const size_t nested_bytes = lift_dim > 0 ? gabo::nested_extremes_lds_doubles(lift_dim, d) * sizeof(double) : 0;
-#ifdef GABO_TR_NO_LAT
-    const bool has_factors = false;
-#else
     const bool has_factors = acq->linv && acq->linv_t;
-#endif
     return gabo::solve_supported(metric == GABO_METRIC_LOG_EUCLIDEAN ? 1 : metric == GABO_METRIC_FROBENIUS ? 2 : 0, acq->n, r, d, n_constraints, has_factors, nested_bytes,
                                  gabo::tr_factor_count(*acq)) ? 1 : 0;
 }

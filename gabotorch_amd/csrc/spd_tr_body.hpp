@@ -48,9 +48,6 @@ struct BuiltinCons {
 };
 
 static __host__ __device__ inline bool builtin_has_kind(const BuiltinCons& B, bool nested) {
-#ifdef GABO_TR_NO_NESTED    /* A/B: the solve kernels without the nested kinds (their eigen-solver of order 24 sets the register budget) */
-    if (nested) return false;
-#endif
     for (int k = 0; k < B.n; ++k)
         if ((B.kind[k] >= 2) == nested) return true;
     return false;
@@ -118,8 +115,8 @@ __device__ __forceinline__ void tridiag_twisted_vector(const double (&dg)[D], co
 
 // lambda_max / lambda_min of the symmetric D x D matrix at `a` and, for each that is asked for, a unit eigenvector - every lane redundantly.
 // The eigenvalues by the eigenvalue-only QL recurrence (the bits sym_eig_reg gives), ONE vector per extreme by the twisted factorisation of the
-// tridiagonal form, carried back through the Householder reflectors.  The strict variant's feasibility test uses the eigenvalues alone; for the
-// constraint gradients it is an opt-in experiment (-DGABO_BUILTIN_TWISTED, see builtin_constraints).
+// tridiagonal form, carried back through the Householder reflectors.  The strict variant's feasibility test uses the eigenvalues alone (the
+// constraint gradients take the full decomposition, see builtin_constraints).
 template <int D>
 __device__ __forceinline__ void eig_extreme_pairs(const double* __restrict__ a, bool need_max, bool need_min, double& lmax, double& lmin,
                                                   double (&vmax)[D], double (&vmin)[D]) {
@@ -194,15 +191,9 @@ __device__ __forceinline__ void builtin_constraints(const double* __restrict__ x
         __syncthreads();
     }
     if (!builtin_has_kind(B, false)) return;
-    bool need_max = false, need_min = false;
-    for (int k = 0; k < B.n; ++k) {
-        need_max = need_max || B.kind[k] == 0;
-        need_min = need_min || B.kind[k] == 1;
-    }
     double lmax, lmin, vmax[D], vmin[D];
-#ifndef GABO_BUILTIN_TWISTED      /* the full decomposition with all D vectors (rounds 3-6).  -DGABO_BUILTIN_TWISTED: eig_extreme_pairs - eigenvalue-only QL +
-                                     one twisted-factorisation vector per extreme; 15.6 k -> 13.6 k cycles in the instrumented build, 694 against 691 us for
-                                     the whole solve in the product build (tools/ab_solve_kernels.sh): not worth another numerical route */
+    // the full decomposition with all D vectors (one twisted-factorisation vector per extreme instead: 694 against 691 us for the whole solve,
+    // not worth another numerical route - CHANGELOG.md, round 6)
     {
         double lam[D], v[dd];
         eig_extremes<D>(x, lam, v);
@@ -220,9 +211,6 @@ __device__ __forceinline__ void builtin_constraints(const double* __restrict__ x
             });
         });
     }
-#else
-    eig_extreme_pairs<D>(x, need_max, need_min, lmax, lmin, vmax, vmin);
-#endif
     for (int k = 0; k < B.n; ++k) {
         if (B.kind[k] >= 2) continue;
         const bool want_max = B.kind[k] == 0;
@@ -279,16 +267,12 @@ __device__ __forceinline__ void tr_begin_part(const double* __restrict__ x, cons
                                               int* __restrict__ status, const BuiltinCons* builtin, bool x_unchanged, double* nlds) {
     const TcgWs& w = t.tcg;
     GABO_TICK(1);
-#ifdef GABO_TCG_BEGIN_LDS      /* A/B: the LDS-phased form everywhere (rounds 2-5) */
-    tcg_begin(x, g, gc, fc, true, delta, w, i, R, D, C, status, mats, x_unchanged);
-#else
     if constexpr (D <= 8) {
         if (x_unchanged) tcg_begin(x, g, gc, fc, true, delta, w, i, R, D, C, status, mats, true);
         else tcg_begin_reg<D>(x, g, gc, fc, true, delta, w, i, R, C, status, mats);
     } else {
         tcg_begin(x, g, gc, fc, true, delta, w, i, R, D, C, status, mats, x_unchanged);
     }
-#endif
     __syncthreads();
     GABO_TICK(2);
     if constexpr (D <= 8) {
@@ -631,12 +615,7 @@ static __device__ __forceinline__ TrFirstStep tr_first_step(double Delta, const 
 // for bit the state those iterations would have left (tests/test_gpu_solve_shortcuts.py compares with gabo_spd_tr_shortcuts(0)).  Hd: H delta_0~ as tcg_step left it
 // (M4 of its LDS tile); the workspace still holds delta_0~, the scalars of tcg_begin and the constraints (tCG's stop path does not touch them).
 // Returns the number of iterations applied; *still becomes false when maxiter is reached.
-#ifdef GABO_TR_FF_INLINE
-#define GABO_FF_INLINE __forceinline__
-#else
-#define GABO_FF_INLINE
-#endif
-static __device__ GABO_FF_INLINE int tr_repeat_rejected(const TcgWs& w, int64_t iw, int64_t Rw, int d, int C, const double* Hd, double delta_cons, double* __restrict__ delta_tr,
+static __device__ int tr_repeat_rejected(const TcgWs& w, int64_t iw, int64_t Rw, int d, int C, const double* Hd, double delta_cons, double* __restrict__ delta_tr,
                                          int64_t* __restrict__ iters, int64_t maxiter, bool* still) {
     const int dd = d * d;
     const double* dl0 = w.delta_w + iw * dd;
@@ -841,14 +820,10 @@ __global__ __launch_bounds__(64, GABO_TR_SOLVE_MIN_WAVES) void spd_tr_solve_kern
     bool cons_fresh = false;          // wave-uniform: the constraints in the workspace belong to the current x
     int last_inner = 0;               // tCG iterations of the previous trust-region iteration
     constexpr int T_ = tri_size(D);
-#ifndef GABO_TR_NO_STEP_CACHE
     __shared__ double step_cache_store[T_ + 1];     // the last proposal's eta~ and a valid flag: see "The same step again" in tr_propose_body
     if (threadIdx.x == 0) step_cache_store[T_] = 0.0;
     __syncthreads();
     double* const step_cache = shortcuts != 0 ? step_cache_store : nullptr;
-#else
-    double* const step_cache = nullptr;
-#endif
     int64_t rec_k = rec != nullptr ? iters[i] : 0;      // gabo_tr_solve_record: index of the outer iteration being recorded
     int n_lazy = 0, n_lazy_accepted = 0, n_reused = 0, n_skipped = 0;      // this restart's shortcut counts (gabo_spd_tr_shortcut_counters)
     for (;;) {
@@ -858,13 +833,8 @@ __global__ __launch_bounds__(64, GABO_TR_SOLVE_MIN_WAVES) void spd_tr_solve_kern
         // proposal, update - and the acquisition GRADIENT there, a third of that evaluation (eigenvectors, logm of every pair, the second
         // triangular product, the adjoint chain), is never used.  So the iteration after a rejected one evaluates the value alone (with the
         // eigenvalue recurrence of the full evaluation: the same bits, sym_eig_reg_values) and the gradient only if the acceptance test passes.
-#ifdef GABO_TR_NO_LAZY_GRADIENT      /* A/B: value and gradient together in every iteration (rounds 1-4) */
-        const bool lazy = false;
-#else
         const bool lazy = cons_fresh && shortcuts != 0;
-#endif
         n_lazy += lazy ? 1 : 0;
-#ifndef GABO_TR_SINGLE_SITE     /* the iteration as tr_propose_body (two inlined acquisition evaluations) + a third evaluation here */
         last_inner = tr_propose_body<D, METRIC>(x + i * dd, g + i * dd, delta_tr[i], nullptr, nullptr, Ps, t, xp, iw, Rw, C, 0, delta_cons, theta,
                                                 kappa, mininner, maxinner, acq, mats, dyn, status, &B, cons_fresh, last_inner == 1, nlds, lazy, step_cache,
                                                 &n_reused);
@@ -885,99 +855,15 @@ __global__ __launch_bounds__(64, GABO_TR_SOLVE_MIN_WAVES) void spd_tr_solve_kern
                                     iw + t.tcg.index_base);
             __syncthreads();
         }
-#else
-        // An experiment of round 6 (-DGABO_TR_SINGLE_SITE; bit-identical results, 720 against 700 us for the solve at 64 restarts: not the default).
-        // The same iteration with ONE call site of the acquisition evaluation: the evaluations of an iteration - at the FD point of every tCG step,
-        // at the proposal, again at the proposal for its gradient once it is known to be accepted - are trips of one loop whose body is "prepare the
-        // next evaluation, evaluate, consume".  acq_eval is inlined wherever it is called, and this kernel sits on a register cliff (512 registers,
-        // 712 B of scratch per lane): every copy moves the whole kernel (a fourth one, the sweep's start, cost 8 %: see above).  Same statements in
-        // the same order as tr_propose_body + the block above: same bits.
-        bool inval = false;
-        {
-            const bool x_unchanged = cons_fresh, fd0_kept = last_inner == 1;
-            const TcgWs& w = t.tcg;
-            double* xfd = t.x_fd + iw * T_;
-            double* egfd = t.eg_fd + iw * T_;
-            double* egfd0 = t.eg_fd0 + iw * T_;
-            double* Fw = t.F + iw * T_ * Ps.n;
-            double* xpm = t.xp_mandel + iw * T_;
-            tr_begin_part<D>(x + i * dd, g + i * dd, delta_tr[i], nullptr, nullptr, t, iw, Rw, C, mats, status, &B, x_unchanged, nlds);
-            GABO_TICK(3);
-            enum { PH_FD = 0, PH_PROP = 1, PH_REGRAD = 2 };
-            int phase = PH_FD, it = 0, inner = 0;
-            double* eg_it = egfd0;
-            for (;;) {
-                const double* ex = xfd;
-                double* ev = t.val_fd + iw;
-                double* eg = eg_it;
-                bool do_eval = true;
-                if (phase == PH_FD) {
-                    ++inner;
-                    if (!(it == 0 && x_unchanged && fd0_kept)) tcg_fd_point(w, iw, D, xfd, mats);
-                    __syncthreads();
-                    GABO_TICK(4);
-                    eg_it = (it == 0) ? egfd0 : egfd;
-                    eg = eg_it;
-                    do_eval = !(it == 0 && x_unchanged);
-                } else if (phase == PH_PROP) {
-                    do_eval = !tr_build_proposal<D>(t, xp, iw, x_unchanged, step_cache, mats);
-                    n_reused += do_eval ? 0 : 1;
-                    GABO_TICK(7);
-                    ex = xpm;
-                    ev = t.fx_prop + iw;
-                    eg = lazy ? nullptr : t.eg_prop + iw * T_;
-                } else {
-                    ex = xpm;
-                    ev = t.fx_prop + iw;
-                    eg = t.eg_prop + iw * T_;
-                }
-                if (do_eval) acq_eval_any<D, METRIC>(ex, Ps, ev, eg, Fw, acq, dyn, status, iw + w.index_base);
-                if (phase == PH_FD) {
-                    __syncthreads();
-                    GABO_TICK(5);
-                    const bool running = tcg_step(w, iw, Rw, D, C, eg_it, 0, delta_cons, theta, kappa, mininner, it, mats);
-                    __syncthreads();
-                    GABO_TICK(6);
-                    ++it;
-                    if (!running || it >= maxinner) phase = PH_PROP;
-                } else if (phase == PH_PROP) {
-                    GABO_TICK(8);
-                    __syncthreads();
-                    if (rec != nullptr && rec_k < rec_cap) {          // (the iterate, its radius and the stop reason of the tCG run that made the proposal)
-                        double* rr = rec + (rec_k * R + i) * (dd + 2);
-                        for (int e = threadIdx.x; e < dd; e += 64) rr[e] = x[i * dd + e];
-                        if (threadIdx.x == 0) {
-                            rr[dd] = delta_tr[i];
-                            rr[dd + 1] = (double)w.stop[iw];
-                        }
-                    }
-                    ++rec_k;
-                    inval = (B.strict && C > 0) ? builtin_infeasible<D>(xp, B, nlds) : false;
-                    if (lazy && tr_would_accept(fx[i], t.fx_prop[iw], t.rhoden[iw], inval, rho_prime, rho_regularization)) {
-                        ++n_lazy_accepted;
-                        phase = PH_REGRAD;
-                    } else {
-                        break;
-                    }
-                } else {
-                    __syncthreads();
-                    break;
-                }
-            }
-            last_inner = inner;
-        }
-#endif
         bool accepted = false;
         const bool still = tr_update_body(x + i * dd, fx + i, g + i * dd, ng + i, delta_tr + i, iters + i, inval, xp, t, iw, D, C, delta_bar,
                                           rho_prime, rho_regularization, mingradnorm, maxiter, mats, &accepted);
         GABO_TICK(9);
-#ifndef GABO_TR_NO_FAST_FORWARD
         if (still && !accepted && last_inner == 1 && t.tcg.running[iw] == 0 && shortcuts != 0 && rec == nullptr && rho_prime < 0.25) {
             bool still_ff = true;
             n_skipped += tr_repeat_rejected(t.tcg, iw, Rw, D, C, mats + 4 * dd, delta_cons, delta_tr + i, iters + i, maxiter, &still_ff);
             if (!still_ff) break;
         }
-#endif
         if (!still) break;
         cons_fresh = !accepted;
     }
@@ -1103,7 +989,7 @@ struct SolveArgs {
 };
 
 // Round 5 history of two instantiations (tools/soak_tr.py found them; tools/repro_solve_fault.py walks the whole table): with the
-// log-Euclidean evaluation's adjoint unrolled in every lane's registers (spd_acq_body.hpp, -DGABO_FROB_REGISTER_ADJOINT) the kernels of that
+// log-Euclidean evaluation's adjoint unrolled in every lane's registers (spd_acq_body.hpp, since replaced) the kernels of that
 // surrogate at d = 7, 8 were 512-register functions with ~3700 vector and ~880 scalar registers spilled, and two of them were wrong AS COMPILED:
 // the generic-workspace solve faulted on a null address at its first launch, the d = 8 propose kernel returned wrong proposals - while the
 // LDS-resident solve of the same source was right.  The adjoint is now shared by the wave through LDS (bit-identical results, 233 registers
@@ -1129,11 +1015,7 @@ static int dispatch_solve(const SolveArgs& a) {
     const size_t nested_bytes = builtin_has_kind(a.B, true) ? nested_extremes_lds_doubles(a.B.big_dim, a.d) * sizeof(double) : 0;
     size_t lds = tr_solve_dynamic_lds(a.P->n, a.r, a.d, a.B.n, &stage_gp, &ws_lds, nested_bytes, &nested_off, tr_factor_count(*a.P));
     if (lds > 64 * 1024) return GABO_ERR_ARG;
-#ifdef GABO_TR_NO_LAT    /* A/B: the runtime-flag kernel everywhere */
-    const bool lat = false;
-#else
     const bool lat = stage_gp && ws_lds && a.P->linv && a.P->linv_t;
-#endif
 #define GABO_SOLVE_LAUNCH(DD, LAT_)                                                                                                \
     hipLaunchKernelGGL((spd_tr_solve_kernel<DD, METRIC, LAT_>), dim3((unsigned)a.r), dim3(64), lds, a.st, a.x, a.fx, a.g, a.ng, a.delta_tr, \
                        a.active, a.iters, *a.P, a.B, a.ws, a.r, a.delta_cons, a.theta, a.kappa, a.mininner, a.maxinner, a.delta_bar, \

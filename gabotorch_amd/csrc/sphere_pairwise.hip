@@ -3,7 +3,7 @@
 //
 // The reference materialises two N1 x N2 x dim tensors and a degenerate bmm; here the inner products run as fp64 MFMA tiles
 // (16 x 16 x 4) and each lane finishes its 16 results in registers.  HBM traffic = the output matrix (8 B per pair).  Measured at
-// N = 4096, dim 10 (tools/ab_sphere.py, tools/sphere_clocks.py): 39-40 us; MFMA + stores alone 24 us, everything but the stores 38 us.
+// N = 4096, dim 10 (tools/ab_sphere.py and per-wave clocks, round 4): 39-40 us; MFMA + stores alone 24 us, everything but the stores 38 us.
 // What bound the 43-us version was not the epilogue but the memory counter (operand loads waiting behind the result stores, see the kernel).
 #include "gabo_device.hpp"
 #include "gabo_mirror.hpp"
@@ -264,7 +264,7 @@ typedef double sph_v4d __attribute__((ext_vector_type(4)));
 // four full 128-byte lines.
 // Issue budget: tools/ubench_mfma_f64.hip shows the f64 matrix pipe and the f64 vector pipe do NOT overlap on gfx950 (MFMA alone 77.8,
 // v_fma_f64 alone 60.6, both together 64.9 TFLOP/s), so per output the MFMA costs 12 issue slots beside the ~48 instructions of the
-// epilogue (27.5 us of the 38-us kernel span; the rest is prologue, the lone-wave tail and store interference: tools/sphere_clocks.py).
+// epilogue (27.5 us of the 38-us kernel span; the rest is prologue, the lone-wave tail and store interference: per-wave clocks, round 4).
 // KS > 0: dim <= 4 KS <= 16 - the wave's x2 fragments stay in registers for all of its row chunks and the block's x1 rows are copied to
 // LDS once, so that the chunk loop contains NO global load.  This is about the memory counter, not about load latency: vmcnt retires in
 // issue order, loads and stores alike, so operand loads issued after a chunk's 16 stores cannot be waited for without also waiting for
@@ -272,8 +272,8 @@ typedef double sph_v4d __attribute__((ext_vector_type(4)));
 // 633 us with the loads behind the stores, 478 us with the stores removed, 369 us for the stores alone).  LDS reads count in lgkmcnt.
 // KS = 0: any dim, operands loaded per chunk.
 constexpr int kSphMaxChunks = 8;
-// four waves per SIMD (128 VGPRs): neither the timestamps of the development build nor the 16 independent table-driven epilogues of a
-// chunk (which the scheduler would otherwise interleave into 160 registers) may cost the fourth wave
+// four waves per SIMD (128 VGPRs): the 16 independent table-driven epilogues of a chunk (which the scheduler would otherwise interleave
+// into 160 registers) may not cost the fourth wave
 #ifndef GABO_SPH_PW_WAVES
 #define GABO_SPH_PW_WAVES 4
 #endif
@@ -286,11 +286,7 @@ constexpr int kSphMaxChunks = 8;
 #ifndef GABO_SPH_PW_EVERY      /* epilogues the scheduler may interleave between two scheduling barriers */
 #define GABO_SPH_PW_EVERY 1
 #endif
-#ifdef GABO_SPH_CLOCKS
-#define GABO_SPH_BOUNDS __launch_bounds__(KT ? 1024 : 256) __attribute__((amdgpu_waves_per_eu(4, 4)))
-#else
 #define GABO_SPH_BOUNDS __launch_bounds__(KT ? 1024 : 256) __attribute__((amdgpu_waves_per_eu((PW || KT) ? GABO_SPH_PW_WAVES : 1, 4)))
-#endif
 #ifndef GABO_SPH_KT_EVERY      /* epilogues of the kernel-value table the scheduler may interleave between two scheduling barriers */
 #define GABO_SPH_KT_EVERY 2
 #endif
@@ -346,10 +342,6 @@ __global__ GABO_SPH_BOUNDS void sphere_pairwise_kernel(const double* __restrict_
             for (int k = kPwFirst * (int)blockDim.x + tid; k < kPwN; k += (int)blockDim.x) pw[k] = kSphPwTab[k] * sc;      // blocks of < 256 threads
         }
     };
-#ifdef GABO_SPH_CLOCKS    /* development: per-wave timestamps (100 MHz) into the output buffer; build with GABO_SPH_PROBE=2 (no result stores) */
-    const uint64_t clk_start = __builtin_amdgcn_s_memrealtime();
-    const uint64_t cyc_start = __builtin_amdgcn_s_memtime();
-#endif
     const int rows = 16 * chunks;
     uint32_t cg, rc;
     if (flags & GABO_SYMMETRIC) {       // x1 is x2: only tiles touching the upper triangle exist (see spd_pairwise.hip)
@@ -439,9 +431,6 @@ __global__ GABO_SPH_BOUNDS void sphere_pairwise_kernel(const double* __restrict_
     }
     if (j0 >= n2) return;
     auto finish_raw = [&](double ip) {
-#if defined(GABO_SPH_PROBE) && GABO_SPH_PROBE == 1     /* development probe: MFMA + stores only */
-        return ip;
-#endif
         if constexpr (KT) return sphere_gauss_finish_kt(ip, gk, kt);
         else if constexpr (PW) return sphere_gauss_finish_pw(ip, gp, pw, tab);
         else if constexpr (MODE == GABO_OUT_GAUSSIAN) return sphere_gauss_finish<SCALED>(ip, g, tab);
@@ -457,18 +446,13 @@ __global__ GABO_SPH_BOUNDS void sphere_pairwise_kernel(const double* __restrict_
         else return ip != ip ? ip : v;
     };
     bool suspect_b = false;
-#ifndef GABO_SPH_NO_NAN_FIXUP
     if constexpr (KS > 0) {
         static_for<KS>([&](auto ss) {
             static_for<4>([&](auto tt) { suspect_b |= sph_suspect(bfrag[decltype(ss)::value][decltype(tt)::value]); });
         });
         suspect_b = __builtin_amdgcn_ballot_w64(suspect_b) != 0;
     }
-#endif
     const uint32_t loff = ((uint32_t)lk * (uint32_t)n2 + (uint32_t)li) * 8u;       // byte offset of the lane inside a 4-row group (n2 < 2^27)
-#ifdef GABO_SPH_CLOCKS
-    const uint64_t clk_loop = __builtin_amdgcn_s_memrealtime();
-#endif
     for (int ch = 0; ch < chunks; ++ch) {
         const int64_t i0 = (int64_t)rc * rows + 16 * ch;
         if (i0 >= n1) break;
@@ -489,14 +473,9 @@ __global__ GABO_SPH_BOUNDS void sphere_pairwise_kernel(const double* __restrict_
                     double* orow = ob + (int64_t)(4 * r) * n2;       // wave-uniform
                     static_for<NTILE>([&](auto tt) {
                         constexpr int t = T0 + decltype(tt)::value;
-#if defined(GABO_SPH_PROBE) && GABO_SPH_PROBE == 2     /* development probe: everything but the stores */
-                        double v_ = finish(acc[t][r]);
-                        if (v_ == 12345.678) *reinterpret_cast<double*>(reinterpret_cast<char*>(orow) + loff + 128u * t) = v_;
-#else
                         double* dst = reinterpret_cast<double*>(reinterpret_cast<char*>(orow) + loff + 128u * t);
                         if constexpr (NT) __builtin_nontemporal_store(finish(acc[t][r]), dst);
                         else *dst = finish(acc[t][r]);
-#endif
                         // one table-driven epilogue at a time: left alone the scheduler interleaves the whole chunk (8 table reads and ~35
                         // registers per output) and the kernel no longer fits the 128 registers of four waves per SIMD
                         if constexpr (PW && GABO_SPH_PW_BARRIER && ((r * NTILE + decltype(tt)::value + 1) % GABO_SPH_PW_EVERY == 0)) __builtin_amdgcn_sched_barrier(0);
@@ -545,9 +524,7 @@ __global__ GABO_SPH_BOUNDS void sphere_pairwise_kernel(const double* __restrict_
                 if constexpr ((PW && GABO_SPH_PW_BARRIER) || KT) __builtin_amdgcn_sched_barrier(0);
             });
             bool suspect = false;
-#ifndef GABO_SPH_NO_NAN_FIXUP     /* A/B: the round-3 kernel (NaN inner products not repaired) */
             static_for<KS>([&](auto ss) { suspect |= sph_suspect(a_cur[decltype(ss)::value]); });
-#endif
             if (__builtin_expect(suspect_b || __builtin_amdgcn_ballot_w64(suspect) != 0, 0)) {
                 // nan_fixup (rare): the chunk's inner products once more, tile by tile; their NaN entries replace what the epilogue stored
                 // (same lane, same address, program order)
@@ -593,17 +570,6 @@ __global__ GABO_SPH_BOUNDS void sphere_pairwise_kernel(const double* __restrict_
             store_tiles(std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{});
         }
     }
-#ifdef GABO_SPH_CLOCKS
-    if ((tid & 63) == 0) {     // records live BEHIND the result matrix: the caller (tools/sphere_clocks.py) allocates 4 doubles per wave more
-        const uint64_t clk_end = __builtin_amdgcn_s_memrealtime();
-        const uint64_t cyc_end = __builtin_amdgcn_s_memtime();
-        double* rec = out + (int64_t)gridDim.y * n1 * n2 + ((int64_t)blockIdx.x * (blockDim.x >> 6) + (tid >> 6)) * 4;
-        rec[0] = (double)clk_start;
-        rec[1] = (double)clk_loop;
-        rec[2] = (double)clk_end;
-        rec[3] = (double)(cyc_end - cyc_start);       // shader cycles entry -> exit
-    }
-#endif
 }
 
 // diag branch: row k of x1 with row k of x2 (sphere_utils_torch.py:45-49)
@@ -679,12 +645,8 @@ extern "C" int gabo_sphere_from_inner(const double* inner, double* out, int64_t 
 namespace gabo {
 // the launch condition of the kernel-value table path (sphere_gauss_finish_kt), in one place
 static bool sphere_uses_ktable(int64_t batch, int64_t n1, int64_t n2, int dim, double beta, int flags) {
-#ifdef GABO_SPH_NO_KT      /* A/B: the round-3 epilogue everywhere */
-    return false;
-#else
     const bool scaled = (flags & GABO_OUT_MASK) == GABO_OUT_GAUSSIAN && beta > 1e-30 && beta < 1000.0;
     return scaled && beta <= kSphKtMaxBeta && dim <= 16 && n2 >= 1024 && (double)batch * (double)n1 * (double)n2 >= (double)(1 << 22);
-#endif
 }
 
 __global__ __launch_bounds__(256) void sphere_ktable_kernel(double beta, double* __restrict__ table) {
@@ -773,13 +735,8 @@ extern "C" int gabo_sphere_pairwise_cached(const double* x1, const double* x2, d
 #define GABO_SPH_NT_BYTES (32ll << 20)
 #endif
         const bool streaming = batch * n1 * n2 * 8 > GABO_SPH_NT_BYTES && !(flags & GABO_SYMMETRIC);
-#ifdef GABO_SPH_NO_PW      /* A/B: the round-2 epilogue (global degree-17 polynomial) for the usual range of beta too */
-#define GABO_SPH_PW_OF(SC) false
-#else
-#define GABO_SPH_PW_OF(SC) SC
-#endif
 #define GABO_SPH_LAUNCH_NT(M, SC, K, NT_)                                                                                          \
-    hipLaunchKernelGGL((gabo::sphere_pairwise_kernel<M, SC, K, NT_, GABO_SPH_PW_OF(SC)>), dim3((unsigned)tiles_x, (unsigned)batch),     \
+    hipLaunchKernelGGL((gabo::sphere_pairwise_kernel<M, SC, K, NT_, SC>), dim3((unsigned)tiles_x, (unsigned)batch),                    \
                        dim3(threads), 0, st, x1, x2, out, n1, n2, dim, x1_batch_stride, x2_batch_stride, (int)col_blocks, (int)row_chunks, \
                        chunks, beta, flags, poly, (const double*)nullptr)
 #define GABO_SPH_LAUNCH_KT(K, NT_)                                                                                                 \

@@ -51,7 +51,7 @@ __device__ __forceinline__ void wave_lds_order() {
 // out: the tridiagonal (dg, e: wave-uniform), 1 / hh_k of the reflectors (ihh) and, when refl != null, the reflectors themselves
 // (u_k, k >= pad, entry j at refl[(k - pad) d + (j - pad)]: at most (d - 2)(d - 1) doubles of a d x d LDS matrix).
 template <int DP>
-__device__ __forceinline__ void wave_tridiagonalize(lds_f64* A, lds_f64* refl, lds_f64* bc, int d, double (&dg)[DP], double (&e)[DP],
+__device__ __forceinline__ void wave_tridiagonalize(lds_f64* A, lds_f64* refl, int d, double (&dg)[DP], double (&e)[DP],
                                                     double (&ihh)[DP >= 3 ? DP - 2 : 1]) {
     const int lane = threadIdx.x & 63;
     const int pad = DP - d;
@@ -73,7 +73,6 @@ __device__ __forceinline__ void wave_tridiagonalize(lds_f64* A, lds_f64* refl, l
             ihh[k] = 0.0;
             return;
         }
-#ifndef GABO_EIGH_LDS_REDUCTION
         // Round 4: no exchange through LDS.  Column k below the diagonal is ONE register pair spread over the lanes k+1 ... DP-1: v_readlane
         // with constant lane indices puts it into scalar registers, where every lane forms |x|^2 and the reflector redundantly (no
         // wave-wide sum) and uses the entries as the scalar operand of its FMAs; q comes back the same way.  One wave-wide sum per column
@@ -111,38 +110,6 @@ __device__ __forceinline__ void wave_tridiagonalize(lds_f64* A, lds_f64* refl, l
         dg[k] = lane_value(a[k], k);
         e[k] = hh == 0.0 ? alpha : -copysign_d(nrm, alpha);
         ihh[k] = inv_hh;
-#else
-        const bool below = lane > k && lane < DP;
-        const double x = below ? a[k] : 0.0;             // column k below the diagonal = entry k of the rows below (symmetry)
-        const double alpha = lane_value(a[k], k + 1);
-        const double nn = wave_allsum(x * x);
-        const double nrm = sqrt_pos(nn);
-        const double hh = __builtin_fma(__builtin_fabs(alpha), nrm, nn);      // u = x + sign(x0)|x| e0, H = I - u u^T / hh
-        const double inv_hh = hh == 0.0 ? 0.0 : rcp(hh);
-        const double u = (lane == k + 1) ? alpha + copysign_d(nrm, alpha) : x;
-        if (lane < DP) bc[2 * lane] = u;
-        if (refl != nullptr && below) refl[(k - pad) * d + (lane - pad)] = u;
-        wave_lds_order();
-        double p = 0.0;
-        static_for<DP - k - 1>([&](auto jj) {
-            constexpr int j = k + 1 + decltype(jj)::value;
-            p = __builtin_fma(a[j], bc[2 * j], p);
-        });
-        p = below ? p * inv_hh : 0.0;
-        const double kap = 0.5 * wave_allsum(u * p) * inv_hh;
-        const double q = __builtin_fma(-kap, u, p);
-        if (lane < DP) bc[2 * lane + 1] = q;
-        wave_lds_order();
-        static_for<DP - k - 1>([&](auto jj) {
-            constexpr int j = k + 1 + decltype(jj)::value;
-            const double ub = bc[2 * j], qb = bc[2 * j + 1];
-            a[j] = __builtin_fma(-q, ub, __builtin_fma(-u, qb, a[j]));
-        });
-        dg[k] = lane_value(a[k], k);
-        e[k] = hh == 0.0 ? alpha : -copysign_d(nrm, alpha);
-        ihh[k] = inv_hh;
-        wave_lds_order();                                // the next step rewrites bc
-#endif
     });
     dg[DP - 2] = lane_value(a[DP - 2], DP - 2);
     e[DP - 2] = lane_value(a[DP - 2], DP - 1);
@@ -460,9 +427,8 @@ __device__ __attribute__((noinline)) void wave_eigh(lds_f64* A, lds_f64* V, lds_
     GABO_EIGH_TICK(0);
     double dg[DP], e[DP], ihh[DP >= 3 ? DP - 2 : 1];
     lds_f64* refl = V;                                    // overwritten by Z at the end
-    wave_tridiagonalize<DP>(A, refl, bc, d, dg, e, ihh);
+    wave_tridiagonalize<DP>(A, refl, d, dg, e, ihh);
     GABO_EIGH_TICK(1);
-#ifndef GABO_EIGH_NO_RQI
     // (d = 7, 8: 21.4 k -> 18.9 k, 25.2 k -> 20.6 k cycles; d <= 6: no gain, the QL path stays - tools/ubench_eigh.hip)
     if constexpr (LANE_GROUPS && DP >= GABO_EIGH_RQI_MIN_DP && DP <= GABO_EIGH_RQI_MAX_DP) {
         if (V != nullptr && (DP > 8 || d >= 7)) {
@@ -480,7 +446,6 @@ __device__ __attribute__((noinline)) void wave_eigh(lds_f64* A, lds_f64* V, lds_
             });
         }
     }
-#endif
     // row `lane` of Q = H_pad ... H_{DP-3}: e_lane^T pushed through the reflectors in order
     double z[DP];
     static_for<DP>([&](auto cc) { z[decltype(cc)::value] = (lane == decltype(cc)::value) ? 1.0 : 0.0; });
@@ -574,7 +539,7 @@ __device__ __attribute__((noinline)) void wave_eig_extremes(lds_f64* A, lds_f64*
     const int half = lane >> 5, r = lane & 31;
     const int pad = DP - d;
     double dg[DP], e[DP], ihh[DP >= 3 ? DP - 2 : 1];
-    wave_tridiagonalize<DP>(A, W, bc, d, dg, e, ihh);
+    wave_tridiagonalize<DP>(A, W, d, dg, e, ihh);
     // ---- Gershgorin bracket of the spectrum of the active block
     double gl = 0.0, gu = 0.0;
     static_for<DP>([&](auto ii) {

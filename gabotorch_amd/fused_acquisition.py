@@ -53,9 +53,6 @@ class FusedAcquisition:
         heldk = getattr(acq.model, "_cache_kinv", None)
         self.kinv = heldk[1] if (heldk is not None and heldk[0] is getattr(acq.model, "_cache", None) and heldk[1] is not None
                                  and heldk[1].device == self.linv.device) else None
-        import os
-        if os.environ.get("GABO_NO_KINV"):          # development A/B: the two triangular factors as in rounds 2-5
-            self.kinv = None
         self.alpha = on(alpha)
         self.train = on(train_x)
         # d <= 12: value + gradient in ONE launch per evaluation (csrc/spd_acq.hip); the training side is factored once here

@@ -1,7 +1,7 @@
 """Development A/B builds: recompile a subset of csrc/*.hip with extra -D flags and link them with the regular objects of every
 other translation unit into gabotorch_amd/libgabo_hip_<tag>.so (select it with GABO_HIP_LIB=...; never the product library).
 
-    python tools/ab_build.py <tag> spd_pairwise.hip[,other.hip] -DGABO_QL_NO_LOOKAHEAD [...]
+    python tools/ab_build.py <tag> spd_pairwise.hip[,other.hip] -DGABO_QL_EPS2=1e-22 [...]
 """
 import os
 import subprocess

@@ -1,4 +1,4 @@
-# reconstruction kernel under the kernel trace (the two commands of tools/collect_profiles_r04.sh, section 4b)
+# reconstruction kernel under the kernel trace (the two commands of the round-4 profile collection, section 4b)
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp PYTHONPATH=$R
 timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prec -o rec -- python $R/tools/recon_profile.py > /tmp/recon.log 2>&1

@@ -1,4 +1,4 @@
-"""Turns the raw outputs of tools/collect_profiles_rNN.sh (gpurun_out/profiles_rNN/) into the files committed under profiles/:
+"""Turns the raw outputs of a round's profile collection (tools/collect_profiles.sh; read from SRC below) into the files committed under profiles/:
 rNN_* copies of the rocprofv3 summaries and profiles/pmc_summary.json (what bench.py's `roofline.traffic` reads).
     python tools/summarise_profiles.py [r03]"""
 import csv
