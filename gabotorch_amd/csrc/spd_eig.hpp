@@ -164,38 +164,42 @@ __device__ __forceinline__ void tridiag_eigenvalues(double (&dg)[D], double (&e2
             } else {
                 idle = done0;
             }
-            if (idle) continue;
-            // Wilkinson shift from the leading 2x2: sigma = d_l - e2_l / (delta + sign(delta) sqrt(delta^2 + e2_l)),
-            // evaluated division-free as d_l - sign(delta) (sqrt(delta^2 + e2_l) - |delta|).  The cancellation of the
-            // rationalised form only costs ~eps |delta| in the SHIFT, which changes the convergence rate, never the result.
-            double delta = 0.5 * (sb - sa);
-            double root = sqrt_shift(__builtin_fma(delta, delta, se));
-            double sigma = sa - copysign_d(root - __builtin_fabs(delta), delta);
-            double gamma = dg[D - 1] - sigma;
-            double p = mul_floor_p(gamma, gamma);
-            double s = 0.0;
-            static_for_down<D - 2, l>([&](auto ii) {
-                constexpr int i = decltype(ii)::value;
-                double bb = (i == l) ? e2l : e2[i];
-                double r = p + bb;
-                if constexpr (i != D - 2) e2[i + 1] = s * r;
-                // one reciprocal serves the step: t = 1/(p r)  =>  1/r = t p.  With f = p (a_i - sigma) - b gamma_old:
-                //   gamma' = c (a_i - sigma) - s gamma_old = f / r = f (t p),     p' = gamma'^2 / c = gamma'^2 r / p = f^2 t
-                // (c itself is never needed; two instructions less per step than forming c, gamma r and (gamma r)^2 t)
-                double t = GABO_QL_RCP(p * r);
-                double ir = t * p;
-                s = bb * ir;
-                double oldgam = gamma;
-                double al = dg[i];
-                double f = __builtin_fma(p, al - sigma, -(bb * oldgam));
-                gamma = ir * f;
-                dg[i + 1] = oldgam + (al - gamma);
-                p = mul_floor_p(f * t, f);
-            });
-            e2[l] = s * p;
-            // (a look-ahead lane's deflated d_l comes back as sigma + (d_l - sigma): a perturbation of an ulp of |sigma| <= |T|, the
-            // size of the backward error of every other step of the sweep)
-            dg[l] = sigma + gamma;
+            // (`if (!idle)` around the sweep, not `if (idle) continue;`: a per-lane `continue` makes the loop itself divergent for the compiler,
+            // which then keeps a per-lane loop state in a VGPR - three v_mov_b32 and two v_cmp_*_i32 per sweep; this way the loop is
+            // wave-uniform, its counter and exit live on the scalar unit, and only the sweep is under the lane mask)
+            if (!idle) {
+                // Wilkinson shift from the leading 2x2: sigma = d_l - e2_l / (delta + sign(delta) sqrt(delta^2 + e2_l)),
+                // evaluated division-free as d_l - sign(delta) (sqrt(delta^2 + e2_l) - |delta|).  The cancellation of the
+                // rationalised form only costs ~eps |delta| in the SHIFT, which changes the convergence rate, never the result.
+                double delta = 0.5 * (sb - sa);
+                double root = sqrt_shift(__builtin_fma(delta, delta, se));
+                double sigma = sa - copysign_d(root - __builtin_fabs(delta), delta);
+                double gamma = dg[D - 1] - sigma;
+                double p = mul_floor_p(gamma, gamma);
+                double s = 0.0;
+                static_for_down<D - 2, l>([&](auto ii) {
+                    constexpr int i = decltype(ii)::value;
+                    double bb = (i == l) ? e2l : e2[i];
+                    double r = p + bb;
+                    if constexpr (i != D - 2) e2[i + 1] = s * r;
+                    // one reciprocal serves the step: t = 1/(p r)  =>  1/r = t p.  With f = p (a_i - sigma) - b gamma_old:
+                    //   gamma' = c (a_i - sigma) - s gamma_old = f / r = f (t p),     p' = gamma'^2 / c = gamma'^2 r / p = f^2 t
+                    // (c itself is never needed; two instructions less per step than forming c, gamma r and (gamma r)^2 t)
+                    double t = GABO_QL_RCP(p * r);
+                    double ir = t * p;
+                    s = bb * ir;
+                    double oldgam = gamma;
+                    double al = dg[i];
+                    double f = __builtin_fma(p, al - sigma, -(bb * oldgam));
+                    gamma = ir * f;
+                    dg[i + 1] = oldgam + (al - gamma);
+                    p = mul_floor_p(f * t, f);
+                });
+                e2[l] = s * p;
+                // (a look-ahead lane's deflated d_l comes back as sigma + (d_l - sigma): a perturbation of an ulp of |sigma| <= |T|, the
+                // size of the backward error of every other step of the sweep)
+                dg[l] = sigma + gamma;
+            }
         }
     });
     // trailing 2x2 [[a, b], [b, c]]: rt1 = larger-magnitude root, rt2 = det / rt1
