@@ -114,9 +114,10 @@ __device__ __forceinline__ void tridiag_eigenvalues(double (&dg)[D], double (&e2
 #define GABO_QL_EPS2 1e-20
 #endif
     // eps2_arg > 0: the caller's threshold (wave-uniform).  The Gaussian kernel VALUE without a distance output tolerates a looser one: dropping
-    // an off-diagonal e^2 <= eps2 |d d'| perturbs sum log^2 lambda by ~eps2 in ABSOLUTE terms (second order), i.e. K = exp(-beta d^2) by
-    // beta eps2 relative - far below its rounding at 1e-16; what the strict 1e-20 protects is the RELATIVE accuracy of a tiny distance
-    // (nearly identical pairs: d ~ 1e-5, d^2 ~ 1e-10), which only the distance and Laplace outputs expose (spd_pairwise_body.hpp).
+    // an off-diagonal e^2 <= eps2 |d d'| perturbs sum log^2 lambda by e^2 f'' in ABSOLUTE terms (second order: up to ~50 eps2 for eigenvalues
+    // between 0.01 and 100), i.e. K = exp(-beta d^2) by beta times that relative - 4e-12 at the 1e-14 in use, inside what the tests allow such a
+    // value; what the strict 1e-20 protects is the RELATIVE accuracy of a tiny distance (nearly identical pairs: d ~ 1e-5, d^2 ~ 1e-10), which
+    // only the distance and Laplace outputs expose (spd_pairwise_body.hpp, GABO_QL_EPS2_GAUSS).
     const double eps2 = eps2_arg > 0.0 ? eps2_arg : GABO_QL_EPS2;
     // QL deflates at the top (index 0) and converges fastest when the small end of a graded matrix sits there (LAPACK's
     // dsterf chooses QL vs QR on the same criterion): reverse the arrays per lane when |d[0]| > |d[D-1]|.  Measured on the

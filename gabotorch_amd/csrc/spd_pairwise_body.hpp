@@ -111,14 +111,35 @@ __device__ __forceinline__ double finish(double dist, double beta, int mode) {
 // 9.8, d = 16: 11.9 -> 14.1 (one wave per SIMD from 15 on).
 #define GABO_PAIR_TWO_WAVE_MAX_DIM 14
 #endif
-template <int D>
+// Deflation threshold of the QL iteration for Gaussian values alone (tridiag_eigenvalues has the argument): a dropped off-diagonal e^2 <= eps2 |d d'|
+// moves d^2 = sum log^2 lambda by e^2 f'' in ABSOLUTE terms, hence K = exp(-beta d^2) by beta times that relative.  With eigenvalues of M between
+// 0.01 and 100 (the benchmark's generator) |d d'| and f'' make it up to ~50 eps2 (measured: K moves by up to 2.2e-11 relative at 1e-13, 4e-12 at 1e-14).
+// The largest decade that leaves every block of tests/test_gpu_pairwise_gauss_finish.py at or below half of its bound is 1e-14: at 1e-13 the test
+// still passes, but its benchmark block stands at 0.7 of the bound and its block of nearly identical pairs (M = I + O(1e-6), d^2 ~1e-10) at 0.8 - 1.1
+// (profiles/gaussonly_ab_items.txt); at 1e-12 the dropped entries are a visible part of such a d^2 itself.  N = 4096, d = 10: 1e-15 -> 1e-14 is -0.6 %.
+#ifndef GABO_QL_EPS2_GAUSS
+#define GABO_QL_EPS2_GAUSS 1e-14
+#endif
+// Two instantiations per dimension, chosen by launch_spd_ai from what it knows at launch time:
+//   <D, false, false>  every output mode, the optional distance output and both forms of the G loads behind run-time branches;
+//   <D, true, true>    Gaussian values alone (no distance leaves the kernel) through the buffer form of the G loads - the Gram of a GP fit,
+//                      the launch the benchmark times.  One pair body, one exp, and a row loop that keeps nothing in scalar registers but
+//                      the row of W, the buffer descriptor and the loop's own state (see the loop).
+// The arithmetic of a pair is the same in both.
+// d = 12 keeps the general instantiation for every launch: there the W row alone is 156 scalar registers, the compiler spills it in both forms
+// (172 against 313 / 2 spills), and the Gaussian-only row loop reads it back with MORE lane moves than one form of the general kernel (569
+// v_readlane_b32 against 785 / 2): measured 1.5 % slower at N = 4096 (3.36 -> 3.41 ms) where d = 5, 10, 13 and 14 gain 1 - 4 %.
+constexpr bool spd_pair_gauss_only_instantiated(int d) { return d > 2 && d != 12; }
+template <int D, bool GAUSS_ONLY, bool BUFFER_ONLY>
 __global__ __launch_bounds__(256, (D > GABO_PAIR_TWO_WAVE_MAX_DIM ? 1 : GABO_PAIR_WAVES)) void spd_ai_pairwise_kernel(const double* __restrict__ Winv, const double* __restrict__ G,
-                                                              double* __restrict__ out, double* __restrict__ dist_out,
+                                                              double* __restrict__ out, double* __restrict__ dist_out_arg,
                                                               int64_t n1, int64_t n2,
                                                               int64_t w_batch_stride, int64_t g_batch_stride, int rows,
                                                               int col_blocks, int row_chunks, int64_t sym_tiles, double beta, int flags) {
     constexpr int T = tri_size(D);
-    const int mode = flags & GABO_OUT_MASK;
+    static_assert(GAUSS_ONLY == BUFFER_ONLY && (spd_pair_gauss_only_instantiated(D) || !GAUSS_ONLY), "instantiations that launch_spd_ai selects");
+    const int mode = GAUSS_ONLY ? GABO_OUT_GAUSSIAN : (flags & GABO_OUT_MASK);
+    double* const dist_out = GAUSS_ONLY ? nullptr : dist_out_arg;
     // small matrices (the latent spaces of the nested kernels: d = 2, 3): the finish is a visible part of a pair's ~140 instructions,
     // so the Gaussian mode uses the table-assisted exp of the write-bound kernels (17 instead of ~37 instructions).  From d = 5 on the
     // scalar registers are taken by the W row and OCML's exp measured faster than any variant with pinned coefficients.
@@ -172,7 +193,7 @@ __global__ __launch_bounds__(256, (D > GABO_PAIR_TWO_WAVE_MAX_DIM ? 1 : GABO_PAI
     double* ob = out + b * n1 * n2;
     // buffer form of the column loads (see SpdGcolBuffer): base = the wave's first column, lane offset = its (clamped) column
     const int64_t jw = j0 + (threadIdx.x & ~63);
-    const bool use_buffer = D > 2 && (int64_t)T * n2 * 8 < (1ll << 31);
+    const bool use_buffer = BUFFER_ONLY || (D > 2 && (int64_t)T * n2 * 8 < (1ll << 31));
     SpdGcolBuffer gbuf;
     {
         const double* gw = G + b * g_batch_stride + (jw < n2 ? jw : n2 - 1);
@@ -200,11 +221,36 @@ __global__ __launch_bounds__(256, (D > GABO_PAIR_TWO_WAVE_MAX_DIM ? 1 : GABO_PAI
     }
     // deflation threshold of the QL iteration: 1e-20 where a distance leaves the kernel (distance and Laplace modes, or a distance output next to the
     // Gaussian values); GABO_QL_EPS2_GAUSS for Gaussian values alone (see tridiag_eigenvalues)
-#ifndef GABO_QL_EPS2_GAUSS
-#define GABO_QL_EPS2_GAUSS 1e-15
-#endif
     double eps2 = (mode == GABO_OUT_GAUSSIAN && !dist_out) ? GABO_QL_EPS2_GAUSS : 0.0;
     asm volatile("" : "+s"(eps2));
+    if constexpr (GAUSS_ONLY && BUFFER_ONLY) {
+        // The row of W takes 2 T scalar registers (110 of about 100 at d = 10), so whatever else is live across a pair is spilled to lanes of a
+        // vector register and read back with v_readlane_b32 (a VALU issue slot each, plus the s_nop behind it).  Hence nothing per row is
+        // recomputed from (i, j, n2, flags, the batch): the W row and the lane's output address advance by constant steps, the row counter is
+        // wave-uniform, and which rows a lane stores (all, none for a column beyond n2, those down to the diagonal in symmetric mode) is one
+        // per-lane bound set before the loop, as in spd_ai_gauss2_kernel.
+        const int nrows = __builtin_amdgcn_readfirstlane((int)(i1 - i0));
+        const int64_t jrel = j - i0;
+        const int rmax = j >= n2 ? -1 : ((flags & GABO_SYMMETRIC) ? (jrel < 0 ? -1 : (jrel > rows - 1 ? rows - 1 : (int)jrel)) : rows - 1);
+        const double* W = Winv + b * w_batch_stride + i0 * T;
+        char* orow = reinterpret_cast<char*>(ob + i0 * n2 + j);      // (never dereferenced by a lane with j >= n2)
+        for (int r = 0; r < nrows; ++r, W += T) {
+            SpdGcolBuffer gb = gbuf;
+            asm volatile("" : "+v"(gb.voff));                  // the 55 G loads stay inside the row loop (see the general loop below)
+            asm volatile("" : "+s"(gb.stride_bytes));
+            const double s = ai_sumsq<D>(W, gb, ltab, eps2);
+            double val;
+            if constexpr (kTabExp) {
+                val = exp_neg_tab(-((s + 1e-15) * beta), ec, ec3, tab);
+                val = s != s ? s : val;                    // (a NaN column of x2 stays NaN: see the general loop)
+            } else {
+                val = exp(-((s + 1e-15) * beta));
+            }
+            if (r <= rmax) *reinterpret_cast<double*>(orow) = val;
+            orow += (unsigned)gb.stride_bytes;                 // n2 * 8 < 2^31 in the buffer form
+        }
+        return;
+    }
     for (int64_t i = i0; i < i1; ++i) {
         const double* W = Winv + b * w_batch_stride + i * T;
         double s;
@@ -470,10 +516,21 @@ static int launch_spd_ai(const double* x1, const double* x2, double* out, double
         else if (streaming) GABO_GAUSS2_LAUNCH(true, false);
         else GABO_GAUSS2_LAUNCH(false, false);
 #undef GABO_GAUSS2_LAUNCH
-    } else
-    hipLaunchKernelGGL((spd_ai_pairwise_kernel<D>), dim3((unsigned)nblocks), dim3(threads), 0, st, W, G, out, dist_out, n1, n2,
-                       (s1 == 0) ? (int64_t)0 : n1 * T, (s2 == 0) ? (int64_t)0 : n2 * T, rows, (int)col_blocks,
-                       (int)row_chunks, sym_tiles, beta, flags);
+    } else {
+#define GABO_PAIR_LAUNCH(...)                                                                                                             \
+        hipLaunchKernelGGL((spd_ai_pairwise_kernel<D, __VA_ARGS__>), dim3((unsigned)nblocks), dim3(threads), 0, st, W, G, out, dist_out, n1, n2, \
+                           (s1 == 0) ? (int64_t)0 : n1 * T, (s2 == 0) ? (int64_t)0 : n2 * T, rows, (int)col_blocks, (int)row_chunks,       \
+                           sym_tiles, beta, flags)
+        // Gaussian values alone, G within reach of a buffer descriptor's 2^31 bytes: the instantiation with nothing else in it (d = 2 has its
+        // own kernel above for that launch)
+        bool gauss_only = false;
+        if constexpr (spd_pair_gauss_only_instantiated(D)) {
+            gauss_only = (flags & GABO_OUT_MASK) == GABO_OUT_GAUSSIAN && !dist_out && (int64_t)T * n2 * 8 < (1ll << 31);
+            if (gauss_only) GABO_PAIR_LAUNCH(true, true);
+        }
+        if (!gauss_only) GABO_PAIR_LAUNCH(false, false);
+#undef GABO_PAIR_LAUNCH
+    }
     if (flags & GABO_SYMMETRIC) {
         int tiles = (int)((n1 + 31) / 32);
         hipLaunchKernelGGL((mirror_upper_kernel<0>), dim3((unsigned)((int64_t)tiles * (tiles + 1) / 2), (unsigned)batch), dim3(256), 0, st,
