@@ -10,10 +10,23 @@
 
 namespace gabo {
 
+// Which end of the tridiagonal sits at index 0, where tridiag_eigenvalues deflates - per lane at run time, or fixed at compile time:
+//   kQlOrientPerLane   reduction from column 0 of M, entries in the order produced; the QL reverses them per lane (see there).  The strict path.
+//   kQlOrientCol0      reduction from column 0, the entries produced LAST at index 0; no per-lane reversal.
+//   kQlOrientLast      reduction from the LAST column of M towards the first (the index map r -> D-1-r on every compile-time index: the
+//                      same instructions, no moves), the entries produced last at index 0; no per-lane reversal.
+// The tridiagonal of a Householder reduction is the Lanczos tridiagonal of M started at a unit vector: its leading entries carry the bulk of
+// the spectrum and the coupling, its trailing ones are small and nearly decoupled - the end a QL iteration wants at its deflation index.  Which
+// fixed form a dimension uses, if any: spd_pair_gauss_only_orientation (spd_pairwise_body.hpp).
+enum QlOrient : int { kQlOrientPerLane = 0, kQlOrientCol0 = 1, kQlOrientLast = 2 };
+
 // m: packed lower triangle of a symmetric D x D matrix (destroyed).  Out: dg[0..D-1] diagonal and
 // e2[0..D-2] squared off-diagonals of the similar tridiagonal matrix (e2[D-1] = 0).
-template <int D>
+template <int D, int ORIENT = kQlOrientPerLane>
 __device__ __forceinline__ void tridiagonalize(double (&m)[tri_size(D)], double (&dg)[D], double (&e2)[D]) {
+    constexpr bool kFromLast = ORIENT == kQlOrientLast, kOutRev = ORIENT != kQlOrientPerLane;
+    // entry (r, c), r >= c, of the matrix the reduction works on: M itself, or M with rows and columns in reverse order
+    auto tri = [](int r, int c) constexpr { return kFromLast ? gabo::tri(D - 1 - c, D - 1 - r) : gabo::tri(r, c); };
     static_for<D - 2>([&](auto kk) {
         constexpr int k = decltype(kk)::value;
         constexpr int n = D - k - 1;  // order of the trailing block; column below the diagonal is x_0..x_{n-1}
@@ -58,15 +71,15 @@ __device__ __forceinline__ void tridiagonalize(double (&m)[tri_size(D)], double 
                 m[tri(k + 1 + r, k + 1 + c)] = v;
             });
         });
-        dg[k] = m[tri(k, k)];
-        e2[k] = nn;
+        dg[kOutRev ? D - 1 - k : k] = m[tri(k, k)];
+        e2[kOutRev ? D - 2 - k : k] = nn;
     });
     if constexpr (D >= 2) {
-        dg[D - 2] = m[tri(D - 2, D - 2)];
+        dg[kOutRev ? 1 : D - 2] = m[tri(D - 2, D - 2)];
         double e = m[tri(D - 1, D - 2)];
-        e2[D - 2] = e * e;
+        e2[kOutRev ? 0 : D - 2] = e * e;
     }
-    dg[D - 1] = m[tri(D - 1, D - 1)];
+    dg[kOutRev ? 0 : D - 1] = m[tri(D - 1, D - 1)];
     e2[D - 1] = 0.0;
 }
 
@@ -103,7 +116,7 @@ __device__ __forceinline__ double mul_floor_p(double a, double b) {
 // only divergence is the iteration count per stage.  An interior off-diagonal that is (or becomes) negligible is
 // simply swept through: the recurrence restarts by itself there (c -> 1, s -> 0).  p > 0 is an invariant (see
 // `mul_floor_p`), hence r = p + bb > 0 and c = p / r > 0: no division can see a zero.  The last 2x2 block is closed form.
-template <int D>
+template <int D, int ORIENT = kQlOrientPerLane>
 __device__ __forceinline__ void tridiag_eigenvalues(double (&dg)[D], double (&e2)[D], const double eps2_arg = 0.0) {
     // Deflation threshold on e2[l] / |d[l] d[l+1]|.  LAPACK uses eps^2 (4.9e-32); 1e-20 is enough here: dropping an
     // off-diagonal e perturbs a SYMMETRIC function of the eigenvalues (sum log^2) only to second order, ~e^2 f'' <= 1e-20,
@@ -121,8 +134,15 @@ __device__ __forceinline__ void tridiag_eigenvalues(double (&dg)[D], double (&e2
     const double eps2 = eps2_arg > 0.0 ? eps2_arg : GABO_QL_EPS2;
     // QL deflates at the top (index 0) and converges fastest when the small end of a graded matrix sits there (LAPACK's
     // dsterf chooses QL vs QR on the same criterion): reverse the arrays per lane when |d[0]| > |d[D-1]|.  Measured on the
-    // benchmark distribution: -9 % QL sweep steps per wave for ~40 selects.
-    if constexpr (D >= 3) {
+    // benchmark distribution: -9 % QL sweep steps per wave against never reversing, for ~40 selects.
+    // The strict path (kQlOrientPerLane) keeps this rule: it serves every launch that is not the Gram of a GP fit (distance and Laplace
+    // outputs, a distance next to the values, d = 12), so it cannot assume a grading, and a fixed end that is wrong costs more than the rule
+    // saves (+13 % sweep steps at d = 10); the bits of its results are pinned by tests/test_gpu_pairwise_gauss_finish.py.  A caller
+    // that fixes the orientation has had tridiagonalize<D, ORIENT> put the end of the reduction at index 0 already: on
+    // the Gram of a GP fit the rule agrees with that for three lanes in four and the fourth sets the pace of its wave's first stage, so the
+    // constant is both cheaper (no compare, no 2 (D - 1) selects of a double) and better (tools/sim/ql_orientation_sim.py, profiles/orient_sim.txt:
+    // d = 10, 118.7 -> 111.3 sweep steps per wave).
+    if constexpr (D >= 3 && ORIENT == kQlOrientPerLane) {
         const bool flip = __builtin_fabs(dg[0]) > __builtin_fabs(dg[D - 1]);
         static_for<D / 2>([&](auto ii) {
             constexpr int i = decltype(ii)::value;

@@ -40,15 +40,19 @@ struct SpdGcolPointer {
     __device__ __forceinline__ double operator[](int k) const { return p[(int64_t)k * stride]; }
 };
 
-template <int D, class GCOL>
+template <int D, int ORIENT = kQlOrientPerLane, class GCOL>
 __device__ __forceinline__ double ai_sumsq(const double* __restrict__ W, const GCOL& Gj, const double* __restrict__ ltab, const double eps2 = 0.0) {
     constexpr int T = tri_size(D);
     // Column `col` of C = W G depends only on column `col` of G:  C[r][col] = sum_{k=col..r} W[r][k] G[k][col].
     // M = C C^T = sum_col C[:,col] C[:,col]^T, so M is accumulated by rank-1 updates and C is never held whole:
     // live state is M (T doubles) + one column of C + one column of G.
+    // (kQlOrientLast, whose reduction starts at the last row of M, takes the columns from the last to the first: the order in which the
+    // reduction wants M is then the order in which it becomes final.  d = 10 listing: with the columns in ascending order that form has 72 scalar spills
+    // and 208 lane moves in the pair body and 233 VGPRs, in descending order none and 194 - against 216 for the other two orientations.)
+    constexpr bool kDescending = ORIENT == kQlOrientLast;
     double m[T];
     static_for<D>([&](auto cc) {
-        constexpr int col = decltype(cc)::value;
+        constexpr int col = kDescending ? D - 1 - decltype(cc)::value : decltype(cc)::value;
         double g[D - col], c[D - col];
         static_for<D - col>([&](auto kk) { g[decltype(kk)::value] = Gj[tri(col + decltype(kk)::value, col)]; });
         static_for<D - col>([&](auto rr) {
@@ -64,14 +68,15 @@ __device__ __forceinline__ double ai_sumsq(const double* __restrict__ W, const G
             constexpr int r = col + decltype(rr)::value;
             static_for<r - col + 1>([&](auto qq) {
                 constexpr int q = col + decltype(qq)::value;
-                // column 0 touches every entry of M first: it initialises, the later columns accumulate
-                m[tri(r, q)] = (col == 0) ? c[r - col] * c[q - col] : __builtin_fma(c[r - col], c[q - col], m[tri(r, q)]);
+                // column 0 touches every entry of M first: it initialises, the later columns accumulate (descending: entry (r, q) is first
+                // touched by column q)
+                m[tri(r, q)] = (kDescending ? col == q : col == 0) ? c[r - col] * c[q - col] : __builtin_fma(c[r - col], c[q - col], m[tri(r, q)]);
             });
         });
     });
     double dg[D], e2[D];
-    tridiagonalize<D>(m, dg, e2);
-    tridiag_eigenvalues<D>(dg, e2, eps2);
+    tridiagonalize<D, ORIENT>(m, dg, e2);
+    tridiag_eigenvalues<D, ORIENT>(dg, e2, eps2);
     double s = 0.0;
     const LogTabRegs lr = LogTabRegs::load();
     static_for<D>([&](auto kk) { double lg = log_tab(dg[decltype(kk)::value], lr, ltab); s = __builtin_fma(lg, lg, s); });
@@ -130,6 +135,30 @@ __device__ __forceinline__ double finish(double dist, double beta, int mode) {
 // (172 against 313 / 2 spills), and the Gaussian-only row loop reads it back with MORE lane moves than one form of the general kernel (569
 // v_readlane_b32 against 785 / 2): measured 1.5 % slower at N = 4096 (3.36 -> 3.41 ms) where d = 5, 10, 13 and 14 gain 1 - 4 %.
 constexpr bool spd_pair_gauss_only_instantiated(int d) { return d > 2 && d != 12; }
+// Orientation of the eigenvalue iteration in the Gaussian-only instantiation (QlOrient, spd_eig.hpp): a compile-time fact per dimension instead
+// of the per-lane reversal rule of the strict path.  Wave-level simulation on the benchmark's generator (tools/sim/ql_orientation_sim.py,
+// profiles/orient_sim.txt; QL VALU per wave-row at 16 per sweep step + 25 per sweep, the rule's own 4 (D - 1) + 1 instructions not counted):
+//     d     per-lane rule   kQlOrientCol0   kQlOrientLast   reduction from the last column, its FIRST entries at index 0
+//     5          635             613             604             705
+//    10         2360            2240            2215            2670
+//    13         3735            3652            3634            4322
+//    16         5499            5325            5324            5984
+//    20         8193            8020            7977            9112
+// kQlOrientLast is the best fixed form, or within 0.1 % of it, at every d from 4 to 20 (d = 3, one QL stage of two steps: 226 / 230 / 215); no stage
+// of any wave takes more than 7 sweeps of the 60 allowed in it, on the benchmark's generator, on nearly identical pairs and at eigenvalue ratio
+// 1e6 alike.  The last column shows why this is a table and not a guess: the wrong end costs 8 - 16 %.  Measured (N = 4096 Gram, per-lane rule -> kQlOrientCol0 ->
+// kQlOrientLast, profiles/orient_ab_bench.txt and profiles/orient_ab_elsewhere.txt): d = 5 0.600 -> 0.580 -> 0.580 ms, d = 10 2.148 -> 2.096 -> 2.094,
+// d = 13 3.982 -> 3.900 -> 3.876, d = 14 5.286 -> 5.162 -> 5.344, d = 16 10.83 -> 10.69 -> 9.18, d = 18 16.02 -> 15.97 -> 12.16.  d = 14 keeps the
+// reduction from column 0: it is the largest dimension budgeted for two waves per SIMD, the compiler spills vector registers to scratch there in
+// every form, and kQlOrientLast measures 1 % slower than the per-lane rule there where kQlOrientCol0 is 2.4 % faster.  (From d = 15 on, one wave per SIMD, most of kQlOrientLast's gain
+// is not the iteration's but the register budget's: with the congruence in descending column order - ai_sumsq - the pair body needs fewer
+// vector registers, d = 10: 216 -> 194, d = 11: 246 -> 232.)
+// A dimension where no fixed form measures faster returns kQlOrientPerLane here and keeps the strict path's code.
+#ifndef GABO_PAIR_ORIENT
+constexpr int spd_pair_gauss_only_orientation(int d) { return d == 14 ? kQlOrientCol0 : kQlOrientLast; }
+#else
+constexpr int spd_pair_gauss_only_orientation(int d) { return GABO_PAIR_ORIENT; }      // (A/B builds: one form for every dimension)
+#endif
 template <int D, bool GAUSS_ONLY, bool BUFFER_ONLY>
 __global__ __launch_bounds__(256, (D > GABO_PAIR_TWO_WAVE_MAX_DIM ? 1 : GABO_PAIR_WAVES)) void spd_ai_pairwise_kernel(const double* __restrict__ Winv, const double* __restrict__ G,
                                                               double* __restrict__ out, double* __restrict__ dist_out_arg,
@@ -238,7 +267,7 @@ __global__ __launch_bounds__(256, (D > GABO_PAIR_TWO_WAVE_MAX_DIM ? 1 : GABO_PAI
             SpdGcolBuffer gb = gbuf;
             asm volatile("" : "+v"(gb.voff));                  // the 55 G loads stay inside the row loop (see the general loop below)
             asm volatile("" : "+s"(gb.stride_bytes));
-            const double s = ai_sumsq<D>(W, gb, ltab, eps2);
+            const double s = ai_sumsq<D, spd_pair_gauss_only_orientation(D)>(W, gb, ltab, eps2);
             double val;
             if constexpr (kTabExp) {
                 val = exp_neg_tab(-((s + 1e-15) * beta), ec, ec3, tab);
