@@ -162,6 +162,28 @@ def spd_ai_gaussian_kernel_grads(x1_mandel, x2_mandel, beta, grad_k):
     return symmetric_matrix_to_vector_mandel(ga), symmetric_matrix_to_vector_mandel(gb)
 
 
+def spd_ai_laplace_kernel_grads(x1_mandel, x2_mandel, beta, grad_k):
+    """Closed-form d/dx1 and d/dx2 (Mandel) of sum(grad_k * K) for K = exp(-beta d)   (kernels_spd.py:157-187; the reference obtains
+    these by autograd through cholesky/inverse/bmm/symeig and the square root, spd_utils_torch.py:87-120).
+
+    The matrix part is that of spd_ai_gaussian_kernel_grads; only the scalar weight differs: with s = d^2 = sum log^2 lam + 1e-15,
+    dK/ds = -beta K / (2 sqrt(s)), finite at coincident points because of the 1e-15 (where exp(-beta d) itself has its kink)."""
+    a = vector_to_symmetric_matrix_mandel(x1_mandel)
+    b = vector_to_symmetric_matrix_mandel(x2_mandel)
+    li = _chol_inv(a)
+    m = np.einsum("...iab,...jbc,...idc->...ijad", li, b, li, optimize=True)
+    lam, v = np.linalg.eigh(m, UPLO="U")
+    lg = np.log(lam)
+    dist = np.sqrt(np.sum(lg * lg, -1) + 1e-15)
+    k = np.exp(-dist * beta)
+    w = np.asarray(grad_k) * (-beta) * k / (2.0 * dist)                     # dLoss/d(d^2_ij)
+    logm = np.einsum("...ab,...b,...cb->...ac", v, lg, v)
+    logm_minv = np.einsum("...ab,...b,...cb->...ac", v, lg / lam, v)
+    ga = np.einsum("...ij,...iba,...ijbc,...icd->...iad", -2.0 * w, li, logm, li, optimize=True)
+    gb = np.einsum("...ij,...iba,...ijbc,...icd->...jad", 2.0 * w, li, logm_minv, li, optimize=True)
+    return symmetric_matrix_to_vector_mandel(ga), symmetric_matrix_to_vector_mandel(gb)
+
+
 def _divided_differences(fun, dfun, lam):
     """first divided differences of `fun` at the eigenvalues, the derivative where two of them coincide (to rounding)"""
     a, b = lam[..., :, None], lam[..., None, :]
@@ -343,12 +365,12 @@ def dlogm_adjoint(a, g):
     V ((V^T G V) o F) V^T with F_kl = (log l_k - log l_l)/(l_k - l_l), F_kk = 1/l_k.  This is what autograd through
     logm_torch (spd_utils_torch.py:13-30) computes, without the 1/(l_k - l_l) blow-up for (nearly) repeated eigenvalues."""
     lam, v = np.linalg.eigh(np.asarray(a, dtype=np.float64), UPLO="U")
-    lg = np.log(lam)
-    dl = lam[..., :, None] - lam[..., None, :]
-    dlg = lg[..., :, None] - lg[..., None, :]
+    # log l_k - log l_l = 2 atanh(z), z = (l_k - l_l) / (l_k + l_l): F = atanh(z) / (z mean) has no cancellation at any gap (the difference of the two
+    # logarithms loses |l_k - l_l| / l digits: 1e-8 relative at a gap of 1e-8, which is more than the gradient tolerances of the device tests)
     mean = 0.5 * (lam[..., :, None] + lam[..., None, :])
-    close = np.abs(dl) <= 1e-9 * mean
-    f = np.where(close, 1.0 / mean, dlg / np.where(close, 1.0, dl))
+    z = (lam[..., :, None] - lam[..., None, :]) / (2.0 * mean)
+    same = z == 0.0
+    f = np.where(same, 1.0, np.arctanh(z) / np.where(same, 1.0, z)) / mean
     inner = np.swapaxes(v, -1, -2) @ np.asarray(g, dtype=np.float64) @ v
     return v @ (inner * f) @ np.swapaxes(v, -1, -2)
 
@@ -372,6 +394,27 @@ def log_euclidean_gaussian_kernel_grads(x1_mandel, x2_mandel, lengthscale, grad_
     gb_log = -np.einsum("...ij,...ijab->...jab", w, diff)
     return (symmetric_matrix_to_vector_mandel(dlogm_adjoint(a, _sym(ga_log))),
             symmetric_matrix_to_vector_mandel(dlogm_adjoint(b, _sym(gb_log))))
+
+
+def frobenius_gaussian_kernel(x1_mandel, x2_mandel, lengthscale):
+    """exp(-||X1_i - X2_j + 1e-15||_F^2 / lengthscale^2)   (kernels_spd.py:213-241)."""
+    d = frobenius_distance(vector_to_symmetric_matrix_mandel(x1_mandel), vector_to_symmetric_matrix_mandel(x2_mandel))
+    return np.exp(-(d * d) / (lengthscale * lengthscale))
+
+
+def frobenius_gaussian_kernel_grads(x1_mandel, x2_mandel, lengthscale, grad_k):
+    """d/dx1, d/dx2 (Mandel) of sum(grad_k * K_Frobenius): dK/dX1 = -2 K (X1 - X2 + 1e-15) / lengthscale^2 as a matrix (the reference
+    obtains it by autograd through spd_utils_torch.py:124-156); the Mandel map is an isometry, so the Mandel gradient is the Mandel
+    vector of the symmetrised matrix gradient."""
+    a = vector_to_symmetric_matrix_mandel(x1_mandel)
+    b = vector_to_symmetric_matrix_mandel(x2_mandel)
+    diff = a[..., :, None, :, :] - b[..., None, :, :, :] + 1e-15
+    d2 = np.sum(diff * diff, axis=(-2, -1))
+    k = np.exp(-d2 / lengthscale ** 2)
+    w = np.asarray(grad_k) * k * (-2.0 / lengthscale ** 2)
+    ga = np.einsum("...ij,...ijab->...iab", w, diff)
+    gb = -np.einsum("...ij,...ijab->...jab", w, diff)
+    return symmetric_matrix_to_vector_mandel(_sym(ga)), symmetric_matrix_to_vector_mandel(_sym(gb))
 
 
 # ------------------------------------------------------------------------------- nested SPD reconstruction (f4)

@@ -45,6 +45,21 @@ def sphere_gaussian_kernel_grads(x1, x2, beta, grad_k):
     return np.einsum("...ij,...jd->...id", w, x2), np.einsum("...ij,...id->...jd", w, x1)
 
 
+def sphere_laplace_kernel_grads(x1, x2, beta, grad_k):
+    """d/dx1, d/dx2 of sum(grad_k * K) for K = exp(-beta d)   (kernels_sphere.py:112-134, where beta = 1 / lengthscale^2).
+    dK/dc = beta K / sqrt(1 - c^2); zero where the clamp is active, as in sphere_gaussian_kernel_grads."""
+    x1 = np.asarray(x1, dtype=np.float64)
+    x2 = np.asarray(x2, dtype=np.float64)
+    ip = np.einsum("...id,...jd->...ij", x1, x2)
+    lo, hi = -1.0 + CLAMP, 1.0 - CLAMP
+    c = np.clip(ip, lo, hi)
+    k = np.exp(-np.arccos(c) * beta)
+    inside = (ip >= lo) & (ip <= hi)
+    dk_dc = np.where(inside, k * (-beta) * (-1.0 / np.sqrt(1.0 - c * c)), 0.0)
+    w = np.asarray(grad_k) * dk_dc
+    return np.einsum("...ij,...jd->...id", w, x2), np.einsum("...ij,...id->...jd", w, x1)
+
+
 def sphere_gaussian_kernel_hvp(x1, x2, beta, grad_k, u):
     """Second order: d/dt grad_x1 [sum(grad_k * K(x1 + t u, x2))] at t = 0 for the Gaussian kernel, Euclidean coordinates (what the reference's
     PyTorch backend returns as `ehess`, pymanopt_addons/tools/autodiff/_pytorch.py:103-116, through sphere_utils_torch.py:12-55 and

@@ -991,12 +991,28 @@ def test_every_trust_region_kernel_instantiation_against_the_torch_solver(flavou
     else:
         kern = (SpdLogEuclideanGaussianKernel if flavour == "le" else SpdFrobeniusGaussianKernel)().double()
         kern.lengthscale = torch.tensor(1.4, dtype=torch.float64)
-    gp = models.ExactGP(t(X), t(y), kern, outputscale=1.0, noise=1e-2)
-    acq = models.ExpectedImprovement(gp, best_f=float(y.min()), maximize=False)
     R = 16
     q = np.linalg.qr(rng.standard_normal((R, d, d)))[0]
     P = np.einsum("nab,nb,ncb->nac", q, rng.uniform(0.5, 2.2, (R, d)), q)
     x0 = ops.matrix_to_mandel(t(0.5 * (P + P.transpose(0, 2, 1))))[:, None]
+    # Guard: the solves must move on an EI that is not ~0.  u = (best_f - mu) / sigma at the 16 starts, from the CPU reference of the acquisition
+    # (tests/_cpu_acquisition.py, nothing from the device): at least half of the starts within |u| <= 6.  Where the (sum log lambda)^2 targets with
+    # best_f = min y do not give that (every d >= 7 at 12 training points: no start within |u| <= 6 at d >= 8, the EI comparison there was one of
+    # values ~0), the targets are standardised and best_f is their median.
+    from tests import _cpu_acquisition as cpu_ref
+    ref_kernel, ref_beta = ("ai_gaussian", kern.beta_float()) if flavour == "ai" else (flavour + "_gaussian", 1.0 / 1.4 ** 2)
+    starts = x0[:, 0].cpu().numpy()
+
+    def starts_in_range(targets, best):
+        u = cpu_ref.acquisition(ref_kernel, starts, X, targets, ref_beta, float(targets.mean()), 1.0, 1e-2, best, "ei", False)["u"]
+        return int((np.abs(u) <= 6.0).sum())
+    best_f = float(y.min())
+    if starts_in_range(y, best_f) < R // 2:
+        y = (y - y.mean()) / y.std()
+        best_f = float(np.median(y))
+    assert starts_in_range(y, best_f) >= R // 2
+    gp = models.ExactGP(t(X), t(y), kern, outputscale=1.0, noise=1e-2)
+    acq = models.ExpectedImprovement(gp, best_f=best_f, maximize=False)
     cons = [functools.partial(scut.max_eigenvalue_constraint_torch, maximum_eigenvalue=2.6),
             functools.partial(scut.min_eigenvalue_constraint_torch, minimum_eigenvalue=0.3)]
     out = {}

@@ -100,3 +100,63 @@ def test_faithful_mandel_loop_equals_the_vectorised_map():
         np.testing.assert_allclose(ospd.vector_to_symmetric_matrix_mandel_faithful(v), ospd.vector_to_symmetric_matrix_mandel(v), rtol=3e-16, atol=0)
     vb = rng.standard_normal((2, 3, 6))
     assert ospd.vector_to_symmetric_matrix_mandel_faithful(vb).shape == (2, 3, 3, 3)
+
+
+def _central_differences(fn, x, gup, h=1e-6):
+    """d/dx of sum(gup * fn(x)) by central differences, entry by entry"""
+    fd = np.zeros_like(x)
+    for idx in np.ndindex(x.shape):
+        xp, xm = x.copy(), x.copy()
+        xp[idx] += h
+        xm[idx] -= h
+        fd[idx] = ((fn(xp) - fn(xm)) * gup).sum() / (2 * h)
+    return fd
+
+
+def test_added_kernel_gradients_by_central_differences_of_the_oracle_value():
+    """The closed-form gradients the oracle has no reference autograd vectors for - affine-invariant Laplace, Frobenius Gaussian, sphere Laplace -
+    against central differences of the oracle's own kernel values, in both arguments (step and tolerance of
+    test_spd_distance_and_laplace_grads_by_finite_differences)."""
+    rng = np.random.default_rng(5)
+    for d in (2, 4):
+        x1 = ospd.symmetric_matrix_to_vector_mandel(_spd(rng, 3, d))
+        x2 = ospd.symmetric_matrix_to_vector_mandel(_spd(rng, 6, d))
+        gup = rng.standard_normal((3, 6))
+        for value, grads, par in ((ospd.spd_ai_laplace_kernel, ospd.spd_ai_laplace_kernel_grads, 0.7),
+                                  (ospd.frobenius_gaussian_kernel, ospd.frobenius_gaussian_kernel_grads, 1.9)):
+            g1, g2 = grads(x1, x2, par, gup)
+            np.testing.assert_allclose(g1, _central_differences(lambda a: value(a, x2, par), x1, gup), rtol=2e-6, atol=1e-7)
+            np.testing.assert_allclose(g2, _central_differences(lambda b: value(x1, b, par), x2, gup), rtol=2e-6, atol=1e-7)
+    for dim in (2, 5):
+        x1 = rng.standard_normal((3, dim)); x1 /= np.linalg.norm(x1, axis=1, keepdims=True)
+        x2 = rng.standard_normal((6, dim)); x2 /= np.linalg.norm(x2, axis=1, keepdims=True)
+        x1, x2 = 0.999 * x1, 0.999 * x2                  # (strictly inside the clamp for the shifted points too)
+        gup = rng.standard_normal((3, 6))
+        g1, g2 = osph.sphere_laplace_kernel_grads(x1, x2, 0.8, gup)
+        np.testing.assert_allclose(g1, _central_differences(lambda a: osph.sphere_laplace_kernel(a, x2, 0.8), x1, gup), rtol=2e-6, atol=1e-7)
+        np.testing.assert_allclose(g2, _central_differences(lambda b: osph.sphere_laplace_kernel(x1, b, 0.8), x2, gup), rtol=2e-6, atol=1e-7)
+    # outside the clamp no gradient passes (autograd `clamp` semantics), as in the Gaussian twin
+    e = np.eye(3)[:1]
+    g1, g2 = osph.sphere_laplace_kernel_grads(e, np.concatenate([e, -e]), 0.8, np.ones((1, 2)))
+    assert not g1.any() and not g2.any()
+
+
+def test_dlogm_adjoint_is_smooth_across_nearly_repeated_eigenvalues():
+    """the divided differences of the logarithm in their cancellation-free form: the adjoint at a gap of 1e-8 and 1e-4 relative lies next to the one at
+    the exactly repeated eigenvalue (a difference of two logarithms would be off by 1e-8 relative at the first), and far from a repeated eigenvalue it is
+    the plain quotient"""
+    rng = np.random.default_rng(9)
+    q = np.linalg.qr(rng.standard_normal((4, 4)))[0]
+    g = rng.standard_normal((4, 4)); g = g + g.T
+    base = np.array([0.7, 1.3, 1.3, 2.1])
+    at = lambda lam: ospd.dlogm_adjoint((q * lam) @ q.T, g)          # noqa: E731
+    ref = at(base)
+    for gap in (1e-8, 1e-4):
+        lam = base.copy(); lam[2] *= 1.0 + gap
+        # first-order change of the adjoint in the gap: |d/dgap| <= |g| / l^2-ish, so 10 gap |ref| bounds it generously
+        np.testing.assert_allclose(at(lam), ref, rtol=0, atol=10 * gap * np.abs(ref).max())
+    lam = np.array([0.5, 0.9, 1.4, 2.2])
+    v = q
+    f = (np.log(lam)[:, None] - np.log(lam)[None, :]) / np.where(np.eye(4, dtype=bool), 1.0, lam[:, None] - lam[None, :])
+    f[np.eye(4, dtype=bool)] = 1.0 / lam
+    np.testing.assert_allclose(at(lam), v @ ((v.T @ g @ v) * f) @ v.T, rtol=1e-12, atol=1e-13)
