@@ -49,6 +49,95 @@ def _randvec(man, x):
     return h / _bm(torch.where(n > 0, n, torch.ones_like(n)), h)
 
 
+# (the reference's defaults, robust_trust_regions.py:116-129, constrained_trust_regions.py:125-142; the native sweep drivers of manifold_optimize.py
+# fill their configurations from the same function)
+def default_limits(man, mininner=1, maxinner=None, Delta_bar=None, Delta0=None, Delta_cons=None):
+    """-> (mininner, maxinner, Delta_bar, Delta0, Delta_cons): inner-iteration limits and radii, defaults for what the caller left open"""
+    if maxinner is None:
+        maxinner = man.dim
+    if Delta_bar is None:
+        Delta_bar = getattr(man, "typicaldist", None) or float(man.dim) ** 0.5
+    if Delta0 is None:
+        Delta0 = Delta_bar / 8
+    if Delta_cons is None:
+        Delta_cons = 1e-6
+    return mininner, maxinner, Delta_bar, Delta0, Delta_cons
+
+
+# The outer iteration's arithmetic, stated once for the generic lock-step plan (_solve) and the plan of device tCG launches.  The Cauchy-point
+# comparison and the ratio test contain no host synchronisation: the tCG-launch plan runs them under graph capture.
+
+def _random_start(man, x, Delta):
+    """use_rand (robust_trust_regions.py:176-181): a tiny random tangent vector per restart, shrunk until it lies inside the trust region"""
+    # (the one function of the three that reads back - it leaves the loop early; use_rand solves are never captured)
+    eps = torch.finfo(x.dtype).eps
+    eta0 = 1e-6 * _randvec(man, x)
+    for _ in range(64):
+        big = man.norm(x, eta0) > Delta
+        if not bool(big.any()):
+            break
+        eta0 = torch.where(_bm(big, eta0), eta0 * float(eps) ** 0.25, eta0)
+    return eta0
+
+
+def _better_of_tcg_and_cauchy(problem, x, fx, g, ng, Delta, eta, Heta):
+    """use_rand (robust_trust_regions.py:196-219): per restart the tCG step or the Cauchy point, whichever has the lower model value -> (eta, Heta)"""
+    man = problem.manifold
+    Hg = problem.hess(x, g, grad_x=g)
+    g_Hg = man.inner(x, g, Hg)
+    safe = torch.where(g_Hg > 0, g_Hg, torch.ones_like(g_Hg))
+    tau_c = torch.where(g_Hg <= 0, torch.ones_like(ng), torch.clamp(ng ** 3 / (Delta * safe), max=1.0))
+    scale = -tau_c * Delta / torch.where(ng > 0, ng, torch.ones_like(ng))
+    eta_c, Heta_c = _bm(scale, g) * g, _bm(scale, Hg) * Hg
+    mdle = fx + man.inner(x, g, eta) + 0.5 * man.inner(x, Heta, eta)
+    mdlec = fx + man.inner(x, g, eta_c) + 0.5 * man.inner(x, Heta_c, eta_c)
+    cauchy = mdlec < mdle
+    return torch.where(_bm(cauchy, eta), eta_c, eta), torch.where(_bm(cauchy, Heta), Heta_c, Heta)
+
+
+def _ratio_test(man, x, fx, g, eta, Heta, fx_prop, invalid, stop_inner, Delta, active, constrained, Delta_bar, rho_regularization, rho_prime):
+    """actual over predicted decrease of the step eta (robust_trust_regions.py:235-354) -> (rho, the radius after the iteration, accept)"""
+    # (fx_prop: the cost at the proposal, +inf where `invalid`, the strict solver's verdict; only active restarts change radius or accept)
+    rhonum = fx - fx_prop
+    rhoden = -man.inner(x, g, eta) - 0.5 * man.inner(x, eta, Heta)
+    rho_reg = torch.clamp(fx.abs(), min=1.0) * torch.finfo(x.dtype).eps * rho_regularization
+    rhonum = rhonum + rho_reg
+    rhoden = rhoden + rho_reg
+    model_decreased = rhoden >= 0
+    rho = torch.where(rhoden == 0, torch.full_like(rhoden, float("nan")), rhonum / rhoden)
+    shrink = (rho < 0.25) | ~model_decreased | torch.isnan(rho) | invalid
+    boundary = (stop_inner == NEGATIVE_CURVATURE) | (stop_inner == EXCEEDED_TR)
+    if constrained:
+        boundary = boundary | (stop_inner == REACHED_CONSTRAINTS)
+    grow = ~shrink & (rho > 0.75) & boundary
+    newDelta = torch.where(shrink, Delta / 4, torch.where(grow, torch.clamp(2 * Delta, max=float(Delta_bar)), Delta))
+    return rho, torch.where(active, newDelta, Delta), active & model_decreased & (rho > rho_prime)
+
+
+# What a device plan keeps per restart - iterate, cost, gradient and its norm, radius, activity, iteration count - from the evaluation at the initial
+# points.  The two launch-per-iteration plans (ncons given) also hand from stage to stage the constraints' values and Riemannian gradients at the
+# iterate, the strict solver's verdict on the proposal and "any restart still active"; the single-launch solve creates none of those.
+class _RestartState:
+    """persistent per-restart tensors of a device plan, updated in place by its launches"""
+
+    def __init__(self, problem, x, Delta0, ncons=None):
+        man, R, dt, dev = problem.manifold, x.shape[0], x.dtype, x.device
+        self.time0 = time.time()
+        fx, eg = problem.fused.cost_egrad(x)
+        problem.n_grad += 1
+        self.x, self.fx = x.detach().clone(), fx.clone()
+        self.g = man.egrad2rgrad(self.x, eg)
+        self.ng = man.norm(self.x, self.g)
+        self.Delta = torch.full((R,), float(Delta0), dtype=dt, device=dev)
+        self.active = torch.ones(R, dtype=torch.bool, device=dev)
+        self.iters = torch.zeros(R, dtype=torch.long, device=dev)
+        if ncons is not None:
+            self.any_active = torch.ones((), dtype=torch.bool, device=dev)
+            self.fc = torch.zeros(R, ncons, dtype=dt, device=dev) if ncons else None
+            self.gc = torch.zeros((ncons,) + tuple(x.shape), dtype=dt, device=dev) if ncons else None
+            self.invalid = torch.zeros(R, dtype=torch.bool, device=dev)
+
+
 class BatchedProblem:
     """cost / Riemannian gradient / Riemannian Hessian-vector product for a batch of restarts.
 
@@ -393,6 +482,13 @@ class BatchedTrustRegions:
                 vals.append(BatchedTrustRegions._call_constraint(con, x).detach().to(x.dtype))
         return torch.stack(vals, dim=1)
 
+    @staticmethod
+    def _infeasible(x_prop, constraints, neq):
+        """-> (R,) the strict solver's verdict on a proposal (constrained_trust_regions.py:932-951): an equality off zero or an inequality below it"""
+        viol = BatchedTrustRegions._constraint_values(x_prop, constraints).clone()
+        viol[:, neq:] = torch.clamp(viol[:, neq:], max=0.0)
+        return viol.abs().sum(1) != 0
+
     # ------------------------------------------------------------------------------------------------- solve
     def solve(self, problem, x=None, eq_constraints=None, ineq_constraints=None, mininner=1, maxinner=None, Delta_bar=None,
               Delta0=None, Delta_cons=None):
@@ -428,14 +524,7 @@ class BatchedTrustRegions:
         x = x.detach().clone()
         R = x.shape[0]
         dt, dev = x.dtype, x.device
-        if maxinner is None:
-            maxinner = man.dim
-        if Delta_bar is None:
-            Delta_bar = getattr(man, "typicaldist", None) or float(man.dim) ** 0.5
-        if Delta0 is None:
-            Delta0 = Delta_bar / 8
-        if Delta_cons is None:
-            Delta_cons = 1e-6
+        mininner, maxinner, Delta_bar, Delta0, Delta_cons = default_limits(man, mininner, maxinner, Delta_bar, Delta0, Delta_cons)
         eqs = list(eq_constraints) if isinstance(eq_constraints, (list, tuple)) else ([eq_constraints] if eq_constraints else [])
         ineqs = list(ineq_constraints) if isinstance(ineq_constraints, (list, tuple)) else ([ineq_constraints] if ineq_constraints else [])
         neq = len(eqs)
@@ -453,62 +542,25 @@ class BatchedTrustRegions:
         active = torch.ones(R, dtype=torch.bool, device=dev)
         iters = torch.zeros(R, dtype=torch.long, device=dev)
         k = 0
-        eps = torch.finfo(dt).eps
         while True:
             if constrained:
                 fc, gc = self._constraint_values_grads(problem, x, eqs + ineqs)
             else:
                 fc, gc = None, []
-            eta0 = None
-            if self.use_rand:                                             # (robust_trust_regions.py:176-181)
-                eta0 = 1e-6 * _randvec(man, x)
-                for _ in range(64):
-                    big = man.norm(x, eta0) > Delta
-                    if not bool(big.any()):
-                        break
-                    eta0 = torch.where(_bm(big, eta0), eta0 * float(eps) ** 0.25, eta0)
+            eta0 = _random_start(man, x, Delta) if self.use_rand else None
             eta, Heta, stop_inner = self._tcg(problem, x, g, Delta, active, mininner, maxinner, fc, gc, neq, Delta_cons, eta0=eta0)
             if self.use_rand:
-                # keep the better of the tCG step and the Cauchy point (:196-219)
-                Hg = problem.hess(x, g, grad_x=g)
-                g_Hg = man.inner(x, g, Hg)
-                safe = torch.where(g_Hg > 0, g_Hg, torch.ones_like(g_Hg))
-                tau_c = torch.where(g_Hg <= 0, torch.ones_like(ng), torch.clamp(ng ** 3 / (Delta * safe), max=1.0))
-                scale = -tau_c * Delta / torch.where(ng > 0, ng, torch.ones_like(ng))
-                eta_c, Heta_c = _bm(scale, g) * g, _bm(scale, Hg) * Hg
-                mdle = fx + man.inner(x, g, eta) + 0.5 * man.inner(x, Heta, eta)
-                mdlec = fx + man.inner(x, g, eta_c) + 0.5 * man.inner(x, Heta_c, eta_c)
-                cauchy = mdlec < mdle
-                eta = torch.where(_bm(cauchy, eta), eta_c, eta)
-                Heta = torch.where(_bm(cauchy, Heta), Heta_c, Heta)
+                eta, Heta = _better_of_tcg_and_cauchy(problem, x, fx, g, ng, Delta, eta, Heta)
             x_prop = man.retr(x, eta)
             fx_prop = problem.cost(x_prop)
             invalid = torch.zeros_like(active)
             if constrained and self.strict_constraints:
-                fcp = self._constraint_values(x_prop, eqs + ineqs)                          # (:932-951)
-                viol = fcp.clone()
-                viol[:, neq:] = torch.clamp(viol[:, neq:], max=0.0)
-                invalid = viol.abs().sum(1) != 0
+                invalid = self._infeasible(x_prop, eqs + ineqs, neq)
                 fx_prop = torch.where(invalid, torch.full_like(fx_prop, float("inf")), fx_prop)
-            rhonum = fx - fx_prop
-            rhoden = -man.inner(x, g, eta) - 0.5 * man.inner(x, eta, Heta)
-            rho_reg = torch.clamp(fx.abs(), min=1.0) * eps * self.rho_regularization
-            rhonum = rhonum + rho_reg
-            rhoden = rhoden + rho_reg
-            model_decreased = rhoden >= 0
-            rho = torch.where(rhoden == 0, torch.full_like(rhoden, float("nan")), rhonum / rhoden)
-            shrink = (rho < 0.25) | ~model_decreased | torch.isnan(rho) | invalid
-            boundary = (stop_inner == NEGATIVE_CURVATURE) | (stop_inner == EXCEEDED_TR)
-            if constrained:
-                boundary = boundary | (stop_inner == REACHED_CONSTRAINTS)
-            grow = ~shrink & (rho > 0.75) & boundary
-            newDelta = torch.where(shrink, Delta / 4, torch.where(grow, torch.clamp(2 * Delta, max=float(Delta_bar)), Delta))
-            Delta_before = Delta
-            Delta = torch.where(active, newDelta, Delta)
-            accept = active & model_decreased & (rho > self.rho_prime)
-            if self.trace is not None:
-                self.trace.append({"x": x.clone(), "Delta": Delta_before, "eta": eta.clone(), "stop_inner": stop_inner.clone(),
-                                   "rho": rho.clone(), "accept": accept.clone(), "active": active.clone(), "fx": fx.clone()})
+            rho, newDelta, accept = _ratio_test(man, x, fx, g, eta, Heta, fx_prop, invalid, stop_inner, Delta, active, constrained, Delta_bar,
+                                                self.rho_regularization, self.rho_prime)
+            self._record(x, Delta, eta, stop_inner, rho, accept, active, fx)
+            Delta = newDelta
             if bool(accept.any()):
                 x = torch.where(_bm(accept, x), x_prop, x)
                 fx = torch.where(accept, fx_prop, fx)
@@ -521,27 +573,31 @@ class BatchedTrustRegions:
             active = active & ~stop
             if not bool(active.any()) or (time.time() - time0) >= self.maxtime:
                 break
-        self.log = {"iterations": k, "per_restart_iterations": iters, "final_cost": fx, "final_gradnorm": ng, "final_radius": Delta,
-                    "cost_evals": problem.n_cost, "grad_evals": problem.n_grad, "time": time.time() - time0}
+        self._set_log(problem, k, iters, fx, ng, Delta, time0)
         return x
+
+    def _record(self, x, Delta, eta, stop_inner, rho, accept, active, fx):
+        """one outer iteration of the generic plan or of the tCG launches into `trace` (when asked for), before the state moves on"""
+        if self.trace is not None:
+            self.trace.append({"x": x.clone(), "Delta": Delta.clone(), "eta": eta.clone(), "stop_inner": stop_inner.clone(),
+                               "rho": rho.clone(), "accept": accept.clone(), "active": active.clone(), "fx": fx.clone()})
+
+    def _set_log(self, problem, k, iters, fx, ng, Delta, time0, **plan):
+        self.log = {"iterations": k, "per_restart_iterations": iters, "final_cost": fx, "final_gradnorm": ng, "final_radius": Delta,
+                    "cost_evals": problem.n_cost, "grad_evals": problem.n_grad, "time": time.time() - time0, **plan}
 
     # ------------------------------------------------------------------------------------------------- device-resident solve
     def _solve_device(self, problem, x, eqs, ineqs, mininner, maxinner, Delta_bar, Delta0, Delta_cons):
-        """solve() for the case _device_tcg_applies: one trust-region iteration is a FIXED sequence of launches on persistent
-        buffers with per-restart masks (no data-dependent host control flow), so with hipGraphs it is captured once and each outer
-        iteration is one replay + one read-back of "any restart still active".  Same arithmetic per restart as solve()."""
-        from .. import ops
-        man, fused = problem.manifold, problem.fused
+        """solve() for the case _device_tcg_applies: chooses among the three device-resident execution plans and runs it"""
+        # In every plan one trust-region iteration is a FIXED sequence of launches on persistent buffers with per-restart masks (no data-dependent
+        # host control flow), with the arithmetic per restart of _solve.  Fastest first: the whole solve as ONE launch, two launches per iteration,
+        # the device tCG launches.  Each plan allocates only what it uses - the single launch neither the tCG handle nor the evaluation and
+        # constraint buffers of the other two: ~10 allocations and fill launches, ~0.1 ms of host time off the front of a 4-ms sweep.
+        fused = problem.fused
         R, d = x.shape[0], x.shape[-1]
-        dt, dev = x.dtype, x.device
         cons = eqs + ineqs
         ncons, neq = len(cons), len(eqs)
         sphere = fused.family == "sphere"
-        # (the random start is drawn between the launches; a trace clones the state between them)
-        graphs = bool(getattr(problem, "use_hip_graphs", False)) and not self.use_rand and self.trace is None
-        # Will the whole solve be ONE launch (decided below by the same tests)?  Then the tCG handle, the evaluation buffers and the
-        # constraint buffers of the multi-launch plans are never touched: not creating them takes ~10 allocations and fill launches
-        # (~0.1 ms of host time) off the front of a 4-ms sweep.
         one_launch = False
         builtins, lift = None, None
         fused_kernels = getattr(fused, "single_launch", False) and getattr(problem, "device_iteration", True) and not self.use_rand
@@ -551,6 +607,7 @@ class BatchedTrustRegions:
         if fused_kernels:
             from ..Riemannian_utils.spd_constraints_utils_torch import builtin_constraint, builtin_lift
             builtins = [builtin_constraint(c) for c in cons]
+            # no constraint needs a host callable (none, or eigenvalue bounds built with functools.partial as in the reference examples)
             solve_ok = (ncons == 0) if sphere else (d <= 8 and neq == 0 and all(b is not None for b in builtins))
             lift = builtin_lift(builtins) if (solve_ok and not sphere) else None      # the nested kinds' mapping (one for all of them)
             solve_ok = solve_ok and lift is not False
@@ -560,101 +617,110 @@ class BatchedTrustRegions:
                 solve_ok = bool(_library().gabo_spd_tr_solve_supported(ctypes.byref(fused.acq_params()), R, d, ncons,
                                                                        0 if lift is None else int(lift[0].shape[0])))
             one_launch = bool(solve_ok and getattr(problem, "device_solve", True) and self.maxtime >= 1000)
-        fused_iteration = propose_ok or one_launch
-        T = None if (sphere or one_launch) else ops.SpdTcg(R, d, ncons, dev)
-        val_buf = None if one_launch else torch.zeros(R, dtype=dt, device=dev)
-        eg_buf = None if one_launch else torch.zeros(R, d * (d + 1) // 2, dtype=dt, device=dev)
-        eps = torch.finfo(dt).eps
-        time0 = time.time()
-        fx, eg = fused.cost_egrad(x)
-        problem.n_grad += 1
+        args = (problem, x, cons, neq, mininner, maxinner, Delta_bar, Delta0, Delta_cons)
+        if one_launch:
+            return self._single_launch_solve(*args, builtins, lift)
+        return self._propose_update_launches(*args) if propose_ok else self._tcg_launches(*args)
 
-        class S:      # persistent state, updated in place
-            pass
-        S.x, S.fx = x.detach().clone(), fx.clone()
-        S.g = man.egrad2rgrad(S.x, eg)
-        S.ng = man.norm(S.x, S.g)
-        S.Delta = torch.full((R,), float(Delta0), dtype=dt, device=dev)
-        S.active = torch.ones(R, dtype=torch.bool, device=dev)
-        S.iters = torch.zeros(R, dtype=torch.long, device=dev)
-        S.any_active = None if one_launch else torch.ones((), dtype=torch.bool, device=dev)
-        step_args = (neq, Delta_cons, self.theta, self.kappa, mininner)
+    @staticmethod
+    def _iteration_kernels(problem, x, ncons):
+        """the fused iteration kernels (csrc/spd_tr.hip, sphere_tr.hip: every wave runs its restart's tCG loop, proposal and evaluations by itself)"""
+        from .. import ops
+        fused, R, d = problem.fused, x.shape[0], x.shape[-1]
+        if fused.family == "sphere":
+            return ops.SphereTr(R, d, ncons, fused.sphere_acq_params(), x.device, exact_hessian=not problem.approx_hessian)
+        return ops.SpdTr(R, d, ncons, fused.acq_params(), fused.train.shape[0], x.device)
 
-        fc_buf = torch.zeros(R, ncons, dtype=dt, device=dev) if (ncons and not one_launch) else None
-        gc_buf = torch.zeros((ncons,) + tuple(x.shape), dtype=dt, device=dev) if (ncons and not one_launch) else None
-        invalid_buf = None if one_launch else torch.zeros(R, dtype=torch.bool, device=dev)
-        strict = bool(ncons and self.strict_constraints)
+    def _single_launch_solve(self, problem, x, cons, neq, mininner, maxinner, Delta_bar, Delta0, Delta_cons, builtins, lift):
+        """gabo_spd_tr_solve / gabo_sphere_tr_solve: every wave iterates its restart to the end"""
+        from .. import ops
+        R, d, dt, dev = x.shape[0], x.shape[-1], x.dtype, x.device
+        sphere = problem.fused.family == "sphere"
+        S = _RestartState(problem, x, Delta0)
+        TR = self._iteration_kernels(problem, x, len(cons))
+        extra = {} if sphere else {"lift": lift}
+        if self.trace is not None:
+            # the launch writes its own record (gabo_tr_solve_record): iterate, radius, tCG stop reason per outer iteration
+            L = d if sphere else d * d
+            extra["record"] = torch.full((int(min(self.maxiter, 1 << 14)), R, L + 2), float("nan"), dtype=dt, device=dev)
+        TR.solve(S.x, S.fx, S.g, S.ng, S.Delta, S.active.view(torch.uint8), S.iters, [b[0] for b in builtins], [b[1] for b in builtins],
+                 bool(cons and self.strict_constraints), Delta_cons, self.theta, self.kappa, mininner, maxinner, Delta_bar, self.rho_prime,
+                 self.rho_regularization, self.mingradnorm, self.maxiter, **extra)
+        if hasattr(TR, "status"):
+            ops._raise_if_not_spd(TR.status, "gabo_spd_tr_solve")       # (when error checking is on: one read-back per solve)
+        k = int(S.iters.max().item())
+        if self.trace is not None:
+            rec = extra["record"]
+            for kk in range(min(k, rec.shape[0])):
+                ran = ~torch.isnan(rec[kk, :, L])
+                self.trace.append({"x": rec[kk, :, :L].reshape(x.shape).clone(), "Delta": rec[kk, :, L].clone(), "active": ran,
+                                   "stop_inner": torch.where(ran, rec[kk, :, L + 1], torch.full_like(rec[kk, :, L], -1.0)).long()})
+        ops.check_deferred()
+        self._set_log(problem, k, S.iters, S.fx, S.ng, S.Delta, S.time0, one_launch_solve=True)
+        return S.x
 
-        def constraints_at_x():                      # user callables (torch): captured only on request, see below
-            fc, gc = self._constraint_values_grads(problem, S.x, cons)
-            fc_buf.copy_(fc)
-            gc_buf.copy_(torch.stack(gc))
-
-        def constraints_at_proposal(A):              # StrictConstrainedTrustRegions (constrained_trust_regions.py:932-951)
-            fcp = self._constraint_values(A["x_prop"], cons)
-            viol = fcp.clone()
-            viol[:, neq:] = torch.clamp(viol[:, neq:], max=0.0)
-            invalid_buf.copy_(viol.abs().sum(1) != 0)
+    def _propose_update_launches(self, problem, x, cons, neq, mininner, maxinner, Delta_bar, Delta0, Delta_cons):
+        """gabo_*_tr_propose (tCG and proposal) and gabo_*_tr_update (evaluation, ratio test, next state): ONE launch each"""
+        R, d, ncons = x.shape[0], x.shape[-1], len(cons)
+        S = _RestartState(problem, x, Delta0, ncons)
+        TR = self._iteration_kernels(problem, x, ncons)
+        active_u8 = S.active.view(torch.uint8)
+        inv_u8 = S.invalid.view(torch.uint8) if (ncons and self.strict_constraints) else None
+        # (where the record below finds the stop reasons of the last tCG run; TcgWs: stop, then running)
+        stop_off = (_library().gabo_sphere_tr_stop_offset(R, d, ncons) // 4 if problem.fused.family == "sphere"
+                    else _library().gabo_spd_tcg_running_offset(R, d, ncons) // 4 - R)
 
         def part_a(sync):
-            T.begin(S.x, S.g, gc_buf, fc_buf, S.active, S.Delta)
-            if self.use_rand:                                             # (robust_trust_regions.py:176-181, 411-415: as _solve / _tcg_begin)
-                eta0 = 1e-6 * _randvec(man, S.x)
-                for _ in range(64):
-                    big = man.norm(S.x, eta0) > S.Delta
-                    if not bool(big.any()):
-                        break
-                    eta0 = torch.where(_bm(big, eta0), eta0 * float(eps) ** 0.25, eta0)
+            return {"x_prop": TR.propose(S.x, S.g, S.Delta, active_u8, S.gc, S.fc, neq, Delta_cons, self.theta, self.kappa, mininner, maxinner)}
+
+        def part_b(A):
+            if self.trace is not None:
+                self.trace.append({"x": S.x.clone(), "Delta": S.Delta.clone(), "active": S.active.clone(), "fx": S.fx.clone(),
+                                   "stop_inner": TR.ws.view(torch.int32)[stop_off:stop_off + R].clone().long()})
+            TR.update(S.x, S.fx, S.g, S.ng, S.Delta, active_u8, S.iters, inv_u8, Delta_bar, self.rho_prime, self.rho_regularization,
+                      self.mingradnorm, self.maxiter)
+            S.any_active.copy_(TR.any_active[0] != 0)
+        return self._iterate(problem, S, cons, neq, part_a, part_b)
+
+    def _tcg_launches(self, problem, x, cons, neq, mininner, maxinner, Delta_bar, Delta0, Delta_cons):
+        """csrc/spd_tcg.hip: per inner iteration an FD-point launch, the fused gradient chain and a step launch; around them _solve's torch arithmetic"""
+        from .. import ops
+        man, fused = problem.manifold, problem.fused
+        R, d, ncons = x.shape[0], x.shape[-1], len(cons)
+        T = ops.SpdTcg(R, d, ncons, x.device)
+        val_buf = torch.zeros(R, dtype=x.dtype, device=x.device)
+        eg_buf = torch.zeros(R, d * (d + 1) // 2, dtype=x.dtype, device=x.device)
+        S = _RestartState(problem, x, Delta0, ncons)
+        strict = bool(ncons and self.strict_constraints)
+
+        def part_a(sync):
+            T.begin(S.x, S.g, S.gc, S.fc, S.active, S.Delta)
+            if self.use_rand:                                             # (robust_trust_regions.py:411-415: as _tcg_begin)
+                eta0 = _random_start(man, S.x, S.Delta)
                 T.begin_rand(eta0, problem.hess(S.x, eta0, grad_x=S.g))
             for _ in range(int(maxinner)):
-                T.step(fused.egrad_mandel(T.fd_point(), active_ptr=T.running_ptr, out=(val_buf, eg_buf)), *step_args)
+                T.step(fused.egrad_mandel(T.fd_point(), active_ptr=T.running_ptr, out=(val_buf, eg_buf)), neq, Delta_cons, self.theta,
+                       self.kappa, mininner)
                 problem.n_grad += 1
                 if sync and not bool(T.any_running.item()):
                     break
             eta, Heta, stop_inner = T.end()
             if self.use_rand:
-                # keep the better of the tCG step and the Cauchy point (:196-219), the statements of _solve
-                Hg = problem.hess(S.x, S.g, grad_x=S.g)
-                g_Hg = man.inner(S.x, S.g, Hg)
-                safe = torch.where(g_Hg > 0, g_Hg, torch.ones_like(g_Hg))
-                tau_c = torch.where(g_Hg <= 0, torch.ones_like(S.ng), torch.clamp(S.ng ** 3 / (S.Delta * safe), max=1.0))
-                scale = -tau_c * S.Delta / torch.where(S.ng > 0, S.ng, torch.ones_like(S.ng))
-                eta_c, Heta_c = _bm(scale, S.g) * S.g, _bm(scale, Hg) * Hg
-                mdle = S.fx + man.inner(S.x, S.g, eta) + 0.5 * man.inner(S.x, Heta, eta)
-                mdlec = S.fx + man.inner(S.x, S.g, eta_c) + 0.5 * man.inner(S.x, Heta_c, eta_c)
-                cauchy = mdlec < mdle
-                eta = torch.where(_bm(cauchy, eta), eta_c, eta)
-                Heta = torch.where(_bm(cauchy, Heta), Heta_c, Heta)
+                eta, Heta = _better_of_tcg_and_cauchy(problem, S.x, S.fx, S.g, S.ng, S.Delta, eta, Heta)
             x_prop = man.retr(S.x, eta)
             fx_prop, eg_prop = fused.cost_egrad(x_prop)
             problem.n_grad += 1
             return {"eta": eta, "Heta": Heta, "stop_inner": stop_inner, "x_prop": x_prop, "fx_prop": fx_prop, "eg_prop": eg_prop}
 
         def part_b(A):
-            eta, Heta, stop_inner, x_prop, eg_prop = A["eta"], A["Heta"], A["stop_inner"], A["x_prop"], A["eg_prop"]
-            fx_prop = A["fx_prop"]
-            invalid = invalid_buf
+            eta, stop_inner, x_prop, fx_prop = A["eta"], A["stop_inner"], A["x_prop"], A["fx_prop"]
             if strict:
-                fx_prop = torch.where(invalid, torch.full_like(fx_prop, float("inf")), fx_prop)
-            rhonum = S.fx - fx_prop
-            rhoden = -man.inner(S.x, S.g, eta) - 0.5 * man.inner(S.x, eta, Heta)
-            rho_reg = torch.clamp(S.fx.abs(), min=1.0) * eps * self.rho_regularization
-            rhonum = rhonum + rho_reg
-            rhoden = rhoden + rho_reg
-            model_decreased = rhoden >= 0
-            rho = torch.where(rhoden == 0, torch.full_like(rhoden, float("nan")), rhonum / rhoden)
-            shrink = (rho < 0.25) | ~model_decreased | torch.isnan(rho) | invalid
-            boundary = (stop_inner == NEGATIVE_CURVATURE) | (stop_inner == EXCEEDED_TR)
-            if ncons:
-                boundary = boundary | (stop_inner == REACHED_CONSTRAINTS)
-            grow = ~shrink & (rho > 0.75) & boundary
-            newDelta = torch.where(shrink, S.Delta / 4, torch.where(grow, torch.clamp(2 * S.Delta, max=float(Delta_bar)), S.Delta))
-            accept = S.active & model_decreased & (rho > self.rho_prime)
-            if self.trace is not None:                                  # (the record of _solve, same keys)
-                self.trace.append({"x": S.x.clone(), "Delta": S.Delta.clone(), "eta": eta.clone(), "stop_inner": stop_inner.clone(),
-                                   "rho": rho.clone(), "accept": accept.clone(), "active": S.active.clone(), "fx": S.fx.clone()})
-            S.Delta.copy_(torch.where(S.active, newDelta, S.Delta))
-            gnew = man.egrad2rgrad(x_prop, eg_prop)                 # the gradient at the proposal IS the gradient at the new x
+                fx_prop = torch.where(S.invalid, torch.full_like(fx_prop, float("inf")), fx_prop)
+            rho, newDelta, accept = _ratio_test(man, S.x, S.fx, S.g, eta, A["Heta"], fx_prop, S.invalid, stop_inner, S.Delta, S.active,
+                                                bool(ncons), Delta_bar, self.rho_regularization, self.rho_prime)
+            self._record(S.x, S.Delta, eta, stop_inner, rho, accept, S.active, S.fx)
+            S.Delta.copy_(newDelta)
+            gnew = man.egrad2rgrad(x_prop, A["eg_prop"])            # the gradient at the proposal IS the gradient at the new x
             S.x.copy_(torch.where(_bm(accept, S.x), x_prop, S.x))
             S.fx.copy_(torch.where(accept, fx_prop, S.fx))
             S.g.copy_(torch.where(_bm(accept, S.g), gnew, S.g))
@@ -663,73 +729,39 @@ class BatchedTrustRegions:
             stop = (S.ng < self.mingradnorm) | (S.iters >= self.maxiter)
             S.active.copy_(S.active & ~stop)
             S.any_active.copy_(S.active.any())
+        return self._iterate(problem, S, cons, neq, part_a, part_b)
 
-        # d <= 12: the two parts are ONE launch each (csrc/spd_tr.hip: every wave runs its restart's whole tCG loop, proposal and
-        # acquisition evaluations by itself)
-        if fused_iteration:
-            if sphere:
-                TR = ops.SphereTr(R, d, ncons, fused.sphere_acq_params(), dev, exact_hessian=not problem.approx_hessian)
-            else:
-                TR = ops.SpdTr(R, d, ncons, fused.acq_params(), fused.train.shape[0], dev)
-            S.active_u8 = S.active.view(torch.uint8)
-            inv_u8 = None if invalid_buf is None else invalid_buf.view(torch.uint8)
+    def _iterate(self, problem, S, cons, neq, part_a, part_b):
+        """the outer loop of the launch-per-iteration plans: part_a(sync) is tCG and proposal, part_b(what part_a returned) ratio test and next state"""
+        from .. import ops
+        ncons = len(cons)
+        strict = bool(ncons and self.strict_constraints)
+        # (the random start is drawn between the launches; a trace clones the state between them)
+        graphs = bool(getattr(problem, "use_hip_graphs", False)) and not self.use_rand and self.trace is None
 
-            def part_a(sync):       # noqa: F811
-                xp = TR.propose(S.x, S.g, S.Delta, S.active_u8, gc_buf, fc_buf, neq, Delta_cons, self.theta, self.kappa, mininner,
-                                maxinner)
-                return {"x_prop": xp}
+        def constraints_at_x():                      # user callables (torch): captured only on request, see below
+            fc, gc = self._constraint_values_grads(problem, S.x, cons)
+            S.fc.copy_(fc)
+            S.gc.copy_(torch.stack(gc))
 
-            # (where the record below finds the stop reasons of the last tCG run; TcgWs: stop, then running)
-            stop_off = (_library().gabo_sphere_tr_stop_offset(R, d, ncons) // 4 if sphere
-                        else _library().gabo_spd_tcg_running_offset(R, d, ncons) // 4 - R)
+        def constraints_at_proposal(A):              # StrictConstrainedTrustRegions
+            S.invalid.copy_(self._infeasible(A["x_prop"], cons, neq))
 
-            def part_b(A):          # noqa: F811
-                if self.trace is not None:
-                    self.trace.append({"x": S.x.clone(), "Delta": S.Delta.clone(), "active": S.active.clone(), "fx": S.fx.clone(),
-                                       "stop_inner": TR.ws.view(torch.int32)[stop_off:stop_off + R].clone().long()})
-                TR.update(S.x, S.fx, S.g, S.ng, S.Delta, S.active_u8, S.iters, inv_u8 if strict else None, Delta_bar, self.rho_prime,
-                          self.rho_regularization, self.mingradnorm, self.maxiter)
-                S.any_active.copy_(TR.any_active[0] != 0)
+        def iteration(sync):
+            if ncons:
+                constraints_at_x()
+            A = part_a(sync)
+            if strict:
+                constraints_at_proposal(A)
+            part_b(A)
 
-            # no constraint needs a host callable (none, or eigenvalue bounds built with functools.partial as in the reference
-            # examples): the whole solve is ONE launch, every wave iterating its restart to the end
-            if one_launch:
-                extra = {} if sphere else {"lift": lift}
-                if self.trace is not None:
-                    # the launch writes its own record (gabo_tr_solve_record): iterate, radius, tCG stop reason per outer iteration
-                    L = d if sphere else d * d
-                    extra["record"] = torch.full((int(min(self.maxiter, 1 << 14)), R, L + 2), float("nan"), dtype=dt, device=dev)
-                TR.solve(S.x, S.fx, S.g, S.ng, S.Delta, S.active_u8, S.iters, [b[0] for b in builtins], [b[1] for b in builtins], strict,
-                          Delta_cons, self.theta, self.kappa, mininner, maxinner, Delta_bar, self.rho_prime, self.rho_regularization,
-                          self.mingradnorm, self.maxiter, **extra)
-                if hasattr(TR, "status"):
-                    ops._raise_if_not_spd(TR.status, "gabo_spd_tr_solve")       # (when error checking is on: one read-back per solve)
-                k = int(S.iters.max().item())
-                if self.trace is not None:
-                    rec = extra["record"]
-                    for kk in range(min(k, rec.shape[0])):
-                        ran = ~torch.isnan(rec[kk, :, L])
-                        self.trace.append({"x": rec[kk, :, :L].reshape(x.shape).clone(), "Delta": rec[kk, :, L].clone(), "active": ran,
-                                           "stop_inner": torch.where(ran, rec[kk, :, L + 1], torch.full_like(rec[kk, :, L], -1.0)).long()})
-                ops.check_deferred()
-                self.log = {"iterations": k, "per_restart_iterations": S.iters, "final_cost": S.fx, "final_gradnorm": S.ng,
-                            "final_radius": S.Delta, "cost_evals": problem.n_cost, "grad_evals": problem.n_grad, "time": time.time() - time0, "one_launch_solve": True}
-                return S.x
-
-        # Execution plan.  Eager: the parts in order, with the inner loop leaving as soon as no restart runs.  hipGraphs: the
-        # launches between two evaluations of the USER's constraint callables form one graph; the callables themselves run
-        # eagerly between replays (they may synchronise) unless the caller vouches for them with capture_constraints=True.
-        capture_cons = bool(getattr(problem, "capture_constraints", False))
-        plan = []               # list of callables executed once per outer iteration
+        # Execution plan.  Eager: the stages in order, with part_a free to read back (sync) so that its inner loop leaves as soon as no restart
+        # runs.  hipGraphs: the launches between two evaluations of the USER's constraint callables form one graph, captured once, so that an
+        # iteration is one replay + one read-back of "any restart still active"; the callables themselves run eagerly between replays (they may
+        # synchronise) unless the caller vouches for them with capture_constraints=True.
         prev_check = None
         if not graphs:
-            holder = {}
-            if ncons:
-                plan.append(constraints_at_x)
-            plan.append(lambda: holder.update(part_a(True)))
-            if strict:
-                plan.append(lambda: constraints_at_proposal(holder))
-            plan.append(lambda: part_b(holder))
+            plan = [lambda: iteration(True)]               # list of callables executed once per outer iteration
         else:
             prev_check = ops.set_error_checking(False)       # a status read-back is a host sync: not capturable
             pool = None
@@ -742,38 +774,29 @@ class BatchedTrustRegions:
                 pool = gr.pool()
                 return gr, out
 
-            if not ncons or capture_cons:
-                def whole():
-                    if ncons:
-                        constraints_at_x()
-                    A = part_a(False)
-                    if strict:
-                        constraints_at_proposal(A)
-                    part_b(A)
-                gr, _ = capture(whole)
-                plan.append(gr.replay)
+            if not ncons or getattr(problem, "capture_constraints", False):
+                gr, _ = capture(lambda: iteration(False))
+                plan = [gr.replay]
             elif not strict:
                 gr, _ = capture(lambda: part_b(part_a(False)))
-                plan += [constraints_at_x, gr.replay]
+                plan = [constraints_at_x, gr.replay]
             else:
                 ga, A = capture(lambda: part_a(False))
                 gb, _ = capture(lambda: part_b(A))
-                plan += [constraints_at_x, ga.replay, lambda: constraints_at_proposal(A), gb.replay]
+                plan = [constraints_at_x, ga.replay, lambda: constraints_at_proposal(A), gb.replay]
         k = 0
         try:
             while True:
                 for stage in plan:
                     stage()
                 k += 1
-                if not bool(S.any_active) or (time.time() - time0) >= self.maxtime:
+                if not bool(S.any_active) or (time.time() - S.time0) >= self.maxtime:
                     break
         finally:
             if prev_check is not None:
                 ops.set_error_checking(prev_check)
-        self.log = {"iterations": k, "per_restart_iterations": S.iters, "final_cost": S.fx, "final_gradnorm": S.ng, "final_radius": S.Delta,
-                    "cost_evals": problem.n_cost, "grad_evals": problem.n_grad, "time": time.time() - time0}
+        self._set_log(problem, k, S.iters, S.fx, S.ng, S.Delta, S.time0)
         return S.x
-
     # ------------------------------------------------------------------------------------------------- truncated CG
     @staticmethod
     def _device_tcg_applies(problem, x, ncons):

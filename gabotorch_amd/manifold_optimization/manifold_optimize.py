@@ -17,7 +17,7 @@ import torch
 from ..models import (BadInitialCandidatesWarning, get_best_candidates, initialize_q_batch, initialize_q_batch_nonneg,
                       is_nonnegative)
 from ..fused_acquisition import FusedAcquisition
-from .batched_trust_regions import BatchedProblem, BatchedTrustRegions
+from .batched_trust_regions import BatchedProblem, BatchedTrustRegions, default_limits
 
 
 def _dist():
@@ -411,6 +411,11 @@ def _native_sweep_plan(acq_function, manifold, solver, q, num_restarts, raw_samp
     device = options.get("device")
     if not (options.get("native_sweep", True) and device is not None):
         return None
+    # (every plan option at its default, all restarts in one batch: both manifolds' drivers)
+    if any(options.get(k, True) is False for k in ("fused_acquisition", "device_tcg", "device_outer", "device_iteration", "device_solve")):
+        return None
+    if options.get("batch_limit", num_restarts) < num_restarts or num_restarts < 1 or raw_samples < 1:
+        return None
     if isinstance(manifold, Sphere):
         if _dist() is not None:
             return None       # (the sphere twin has no sharded form: the Python path below shards it)
@@ -418,10 +423,6 @@ def _native_sweep_plan(acq_function, manifold, solver, q, num_restarts, raw_samp
         if not (q == 1 and bounds is None and not solver_init_conds and sample_type == torch.float64 and isinstance(solver, BatchedTrustRegions)
                 and not solver.use_rand and solver.maxtime >= 1000 and solver.trace is None and not equality_constraints
                 and not inequality_constraints and pre_processing_manifold is None and post_processing_manifold is None):
-            return None
-        if any(options.get(k, True) is False for k in ("fused_acquisition", "device_tcg", "device_outer", "device_iteration", "device_solve")):
-            return None
-        if options.get("batch_limit", num_restarts) < num_restarts or num_restarts < 1 or raw_samples < 1:
             return None
         dev = torch.device(device)
         if dev.type != "cuda":
@@ -434,10 +435,6 @@ def _native_sweep_plan(acq_function, manifold, solver, q, num_restarts, raw_samp
     if not (q == 1 and bounds is None and not solver_init_conds and approx_hessian and sample_type == torch.float64
             and isinstance(solver, BatchedTrustRegions) and not solver.use_rand and solver.maxtime >= 1000
             and solver.trace is None and not equality_constraints):
-        return None
-    if any(options.get(k, True) is False for k in ("fused_acquisition", "device_tcg", "device_outer", "device_iteration", "device_solve")):
-        return None
-    if options.get("batch_limit", num_restarts) < num_restarts or num_restarts < 1 or raw_samples < 1:
         return None
     if not (isinstance(manifold, PositiveDefinite) and 2 <= manifold._n <= 8):
         return None
@@ -571,9 +568,9 @@ def _native_sweep(plan, acq_function, solver, num_restarts, raw_samples, options
     for k, b in enumerate(plan["builtins"]):
         cfg.constraint_kind[k], cfg.constraint_bound[k] = int(b[0]), float(b[1])
     cfg.strict = 1 if solver.strict_constraints else 0
-    delta_bar = getattr(man, "typicaldist", None) or float(man.dim) ** 0.5          # (BatchedTrustRegions._solve's defaults)
-    cfg.delta_bar, cfg.delta0, cfg.delta_cons = float(delta_bar), float(delta_bar) / 8, 1e-6
-    cfg.theta, cfg.kappa, cfg.mininner, cfg.maxinner = float(solver.theta), float(solver.kappa), 1, int(man.dim)
+    mininner, maxinner, delta_bar, delta0, cfg.delta_cons = default_limits(man)
+    cfg.delta_bar, cfg.delta0 = float(delta_bar), float(delta0)
+    cfg.theta, cfg.kappa, cfg.mininner, cfg.maxinner = float(solver.theta), float(solver.kappa), int(mininner), int(maxinner)
     cfg.rho_prime, cfg.rho_regularization = float(solver.rho_prime), float(solver.rho_regularization)
     cfg.mingradnorm, cfg.maxiter = float(solver.mingradnorm), int(solver.maxiter)
     nonneg, eta, alpha = _selection(acq_function, options)
@@ -710,9 +707,9 @@ def _native_sweep_sphere(plan, acq_function, solver, num_restarts, raw_samples, 
     dim, R = int(man._n), int(num_restarts)
     cfg = _lib.SphereSweepConfig()
     cfg.acq = fused.sphere_acq_params()
-    delta_bar = getattr(man, "typicaldist", None) or float(man.dim) ** 0.5
-    cfg.delta_bar, cfg.delta0 = float(delta_bar), float(delta_bar) / 8
-    cfg.theta, cfg.kappa, cfg.mininner, cfg.maxinner = float(solver.theta), float(solver.kappa), 1, int(man.dim)
+    mininner, maxinner, delta_bar, delta0, _ = default_limits(man)
+    cfg.delta_bar, cfg.delta0 = float(delta_bar), float(delta0)
+    cfg.theta, cfg.kappa, cfg.mininner, cfg.maxinner = float(solver.theta), float(solver.kappa), int(mininner), int(maxinner)
     cfg.exact_hessian = 1 if plan["exact_hessian"] else 0
     cfg.rho_prime, cfg.rho_regularization = float(solver.rho_prime), float(solver.rho_regularization)
     cfg.mingradnorm, cfg.maxiter = float(solver.mingradnorm), int(solver.maxiter)
