@@ -5,7 +5,7 @@ gabo_sphere_bound_constraints}.py: the constraint callables, the constrained `ma
 selects - AugmentedLagrangeMethod(maxiter=200, inner_solver=TrustRegions(maxiter=200), gammas_fact=0.05) by default for the first two
 (their `solver_name = 'ALM'`), ConstrainedTrustRegions(maxiter=200) for the bounds (and for `--solver CTR`) - EI, 5 restarts / 100 raw samples.
 
-    python examples/gabo_sphere_constraints.py --kind equality|inequality|bounds [--solver ALM|CTR] [--iters 10]
+    python examples/gabo_sphere_constraints.py --kind equality|inequality|bounds [--solver ALM|CTR] [--iters 10] [--builtin-constraints]
 
 The augmented-Lagrangian method runs on all restarts in lock step (its inner trust-region solves batched, the acquisition through the fused
 HIP evaluation; `options={"batched_alm": False}`: restart by restart on the host, as the reference drives it, manifold_optimize.py:207-220) -
@@ -31,8 +31,15 @@ from gabotorch_amd.manifold_optimization.robust_trust_regions import TrustRegion
 BETA_MIN = {3: 6.5, 4: 2.0, 5: 1.2, 10: 0.6, 20: 0.35, 50: 0.21, 100: 0.21}     # gabo_sphere_equality_constraints.py:158-171
 
 
-def constraints(kind, dim):
-    """-> (equality constraints, inequality constraints, sampler of feasible points, feasibility test on a numpy point)"""
+def constraints(kind, dim, builtin=False):
+    """-> (equality constraints, inequality constraints, sampler of feasible points, feasibility test on a numpy point).  builtin: the same
+    constraints built with functools.partial over the library's functions (Riemannian_utils/sphere_constraints_utils_torch.py), which the
+    trust-region kernels evaluate themselves: ConstrainedTrustRegions then solves every sweep in one launch."""
+    import functools
+
+    from gabotorch_amd.Riemannian_utils import sphere_constraints_utils_torch as scu
+    lower = lambda i, b: functools.partial(scu.coordinate_lower_bound_constraint_torch, index=i, lower_bound=b)      # noqa: E731
+    upper = lambda i, b: functools.partial(scu.coordinate_upper_bound_constraint_torch, index=i, upper_bound=b)      # noqa: E731
     if kind == "equality":                      # gabo_sphere_equality_constraints.py:100-118: the great circle x[1] = yc
         yc = 0.0
 
@@ -42,7 +49,7 @@ def constraints(kind, dim):
             x[1] = yc
             x[idx] = x[idx] / np.linalg.norm(x[idx]) * np.sqrt(1 - yc ** 2)
             return x
-        return [lambda x: x[..., 1] - yc], None, sample, lambda p: abs(p[1] - yc) < 2e-3
+        return [lower(1, yc) if builtin else (lambda x: x[..., 1] - yc)], None, sample, lambda p: abs(p[1] - yc) < 2e-3
     if kind == "inequality":                    # gabo_sphere_inequality_constraints.py:100-141: the cap of half-angle pi / 4 around e_0
         angle = np.pi / 4.0
 
@@ -60,11 +67,15 @@ def constraints(kind, dim):
                 x[1:] = x[1:] / np.linalg.norm(x[1:]) * s
             x[0] = np.sqrt(max(1 - np.sum(x[1:] ** 2), 0.0))
             return x
+        if builtin:
+            domain = functools.partial(scu.geodesic_ball_constraint_torch, center=torch.eye(dim, dtype=torch.float64)[0], angle=angle)
         return None, [domain], sample, lambda p: np.arccos(np.clip(p[0], -1, 1)) < angle + 2e-3
     if kind == "bounds":                        # gabo_sphere_bound_constraints.py:94-131 (S^2 only)
         assert dim == 3
         xl, yl, yu, zl, zu = 0.0, -0.6, 0.6, -0.6, 0.6
         cons = [lambda x: x[..., 0] - xl, lambda x: x[..., 1] - yl, lambda x: yu - x[..., 1], lambda x: x[..., 2] - zl, lambda x: zu - x[..., 2]]
+        if builtin:
+            cons = [lower(0, xl), lower(1, yl), upper(1, yu), lower(2, zl), upper(2, zu)]
 
         def sample():
             while True:
@@ -76,11 +87,12 @@ def constraints(kind, dim):
     raise ValueError(kind)
 
 
-def run(kind="equality", solver_name=None, dim=3, iters=10, restarts=5, raw=100, seed=1234, device="cuda:0", verbose=True, alm_maxiter=200):
+def run(kind="equality", solver_name=None, dim=3, iters=10, restarts=5, raw=100, seed=1234, device="cuda:0", verbose=True, alm_maxiter=200,
+        builtin_constraints=False):
     np.random.seed(seed)
     torch.manual_seed(seed)
     man = manifolds.Sphere(dim)
-    eqs, ineqs, sample, feasible = constraints(kind, dim)
+    eqs, ineqs, sample, feasible = constraints(kind, dim, builtin_constraints)
     man.rand = sample                           # "Replace sample function of the manifold by the constrained sampling" (:118)
     objective = lambda x: ackley_function_sphere(x, man)      # noqa: E731
     x_data = torch.tensor(np.stack([man.rand() for _ in range(5)]), device=device)
@@ -113,5 +125,6 @@ if __name__ == "__main__":
     ap.add_argument("--solver", default=None, choices=["ALM", "CTR"])
     ap.add_argument("--dim", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--builtin-constraints", action="store_true", help="the library's constraint functions instead of lambdas")
     a = ap.parse_args()
-    run(a.kind, a.solver, a.dim, a.iters)
+    run(a.kind, a.solver, a.dim, a.iters, builtin_constraints=a.builtin_constraints)

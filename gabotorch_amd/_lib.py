@@ -25,6 +25,7 @@ GABO_GP_MLL_LARGE_MAX_N = 2048
 GABO_METRIC_AFFINE_INVARIANT, GABO_METRIC_LOG_EUCLIDEAN, GABO_METRIC_FROBENIUS = 0, 8, 16
 GABO_CONSTRAINT_MAX_EIGENVALUE, GABO_CONSTRAINT_MIN_EIGENVALUE = 0, 1
 GABO_CONSTRAINT_MAX_EIGENVALUE_NESTED, GABO_CONSTRAINT_MIN_EIGENVALUE_NESTED = 2, 3
+GABO_SPHERE_CONSTRAINT_COORD_LOWER, GABO_SPHERE_CONSTRAINT_COORD_UPPER, GABO_SPHERE_CONSTRAINT_GEODESIC_BALL = 0, 1, 2
 GABO_TR_SHORTCUT_COUNTERS = 5            # value first, value first then accepted, step reused, fast-forwarded, generic-workspace restarts
 GABO_RECON_AFFINE_INVARIANT, GABO_RECON_LOG_EUCLIDEAN = 0, 1
 GABO_RECON_MAX_LOOKAHEAD = 4
@@ -156,6 +157,10 @@ SIGNATURES = {
     "gabo_sphere_tr_propose": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _I64, _I, _I, _D, _D, _D, _I, _I, _I, _P, _P]),
     "gabo_sphere_tr_update": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I, _I, _D, _D, _D, _D, _I64, _P, _P]),
     "gabo_sphere_tr_solve": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I64, _D, _D, _I, _I, _I, _D, _D, _D, _D, _I64, _P]),
+    "gabo_sphere_tr_solve_constrained": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I64, _D, _D, _I, _I, _I, _D, _D, _D, _D, _I64,
+                                              _I, _I, _P, _P, _P, _P, _I, _I, _D, _P]),
+    "gabo_sphere_constraints_eval": (_I, [_P, _I64, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "gabo_sphere_tr_solve_lds_resident": (_I, [_P, _I64, _I]),
     "gabo_spd_logm_mandel_backward": (_I, [_P, _P, _P, _I64, _I, _P]),
     "gabo_frobenius_backward": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _I64, _I64, _I64, _I64, _I64, _D, _I, _D, _P]),
     "gabo_sphere_manifold_op": (_I, [_I, _P, _P, _P, _P, _P, _I64, _I, _P]),

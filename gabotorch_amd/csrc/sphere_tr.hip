@@ -7,7 +7,9 @@
 //                           ([3P], SURVEY App. B: inner = dot, proj(x, u) = u - <x, u> x, retr = normalise(x + u),
 //                           transp(x1, x2, u) = proj(x2, u)), then the proposal and the acquisition at the proposal
 //   gabo_sphere_tr_update   rho test and state update (robust_trust_regions.py:236-330)
-//   gabo_sphere_tr_solve    the whole solve in one launch when there are no constraints
+//   gabo_sphere_tr_solve    the whole solve in one launch; gabo_sphere_tr_solve_constrained the same with the library's own sphere
+//                           constraints (sphere_constraints_utils_torch.py: coordinate bounds, geodesic ball) evaluated by the wave
+//   gabo_sphere_constraints_eval   values and Riemannian gradients of those constraints at R points, one launch
 // The scalar logic of the tCG iteration is tcg_step_core of spd_tcg_body.hpp (shared with the SPD kernels).
 #include "spd_tcg_body.hpp"
 
@@ -297,7 +299,8 @@ static __device__ __forceinline__ double dotg(const double* a, const double* b, 
     return wave_sum(s);
 }
 
-// tCG + proposal + acquisition at the proposal for restart i.  lds: 6 dim doubles; dyn: 3 n doubles.
+// tCG + proposal + acquisition at the proposal for restart i.  lds: 6 dim doubles; dyn: 3 n doubles.  gc / fc == nullptr with C > 0: the
+// constraint gradients and values are already in the workspace (w.gc, w.fc: the single-launch solve evaluates them there, as tcg_begin).
 static __device__ __forceinline__ void sph_propose_body(const double* __restrict__ x, const double* __restrict__ g, double delta_tr,
                                         const double* __restrict__ gc, const double* __restrict__ fc, const SphAcq& P, const SphWs& w,
                                         int64_t i, int64_t R, int C, int neq, double delta_cons, double theta, double kappa,
@@ -326,7 +329,7 @@ static __device__ __forceinline__ void sph_propose_body(const double* __restrict
         eta[e] = 0.0;
         heta[e] = 0.0;
     }
-    for (int k = 0; k < C; ++k)
+    for (int k = 0; gc != nullptr && k < C; ++k)
         for (int e = threadIdx.x; e < dim; e += 64) w.gc[((int64_t)k * R + i) * dim + e] = gc[((int64_t)k * R + i) * dim + e];
     __syncthreads();
     const double r2 = dotg(s2, s2, dim);
@@ -348,7 +351,7 @@ static __device__ __forceinline__ void sph_propose_body(const double* __restrict
         sc[SC_NORM_R0] = __builtin_sqrt(r2 > 0.0 ? r2 : 0.0);
         w.stop[i] = TCG_MAX_INNER_ITER;
         w.running[i] = 1;
-        for (int k = 0; k < C; ++k) { w.fc[i * C + k] = fc[i * C + k]; w.fcg_pe[i * C + k] = 0.0; }
+        for (int k = 0; k < C; ++k) { if (fc != nullptr) w.fc[i * C + k] = fc[i * C + k]; w.fcg_pe[i * C + k] = 0.0; }
     }
     __syncthreads();
     TcgVecs v{gi, eta, heta, rr, delta, w.gc + i * dim, (int64_t)R * dim, sc, w.fc + i * C, w.fcg_pe + i * C, w.stop + i, w.running + i};
@@ -466,6 +469,74 @@ static __device__ __forceinline__ bool sph_update_body(double* __restrict__ x, d
     return !(ngi < mingradnorm || it >= maxiter);
 }
 
+// The library's own sphere constraints (Riemannian_utils/sphere_constraints_utils_torch.py; kinds GABO_SPHERE_CONSTRAINT_*), equalities first.
+// A kernel argument: kind / index / bound are read with wave-uniform indices.
+struct SphCons {
+    int n, neq, strict;
+    int kind[kMaxCons];
+    int index[kMaxCons];        // the coordinate, or the row of `centres` for the ball
+    double bound[kMaxCons];
+    double delta_cons;
+    const double* centres;      // n_centres x dim
+};
+
+// value of constraint k at x (dim doubles, global or LDS), written as the torch function states it; the same in every lane.
+// *inner: <x, centre> of a ball.
+static __device__ __forceinline__ double sph_cons_value(const double* __restrict__ x, int dim, const SphCons& K, int k, double* inner) {
+    const int kind = K.kind[k], j = K.index[k];
+    const double b = K.bound[k];
+    if (kind == GABO_SPHERE_CONSTRAINT_GEODESIC_BALL) {
+        const double c = dotg(x, K.centres + (int64_t)j * dim, dim);
+        *inner = c;
+        const double cc = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
+        return b - acos(cc);
+    }
+    return kind == GABO_SPHERE_CONSTRAINT_COORD_LOWER ? x[j] - b : b - x[j];
+}
+
+// values fc[k] and (gc != nullptr) Riemannian gradients proj_x(egrad) gc[k * gc_stride + e] of the K.n constraints at x.  The ball's gradient is
+// zero where |<x, centre>| >= 1 (the clip is flat outside and acos has no derivative at +-1: geodesic_ball_constraint_torch defines it so).
+static __device__ __forceinline__ void sph_cons_eval(const double* __restrict__ x, int dim, const SphCons& K, double* __restrict__ fc,
+                                                     double* __restrict__ gc, int64_t gc_stride) {
+    for (int k = 0; k < K.n; ++k) {
+        double c = 0.0;
+        const double v = sph_cons_value(x, dim, K, k, &c);
+        if (threadIdx.x == 0) fc[k] = v;
+        if (gc == nullptr) continue;
+        double* gk = gc + (int64_t)k * gc_stride;
+        if (K.kind[k] == GABO_SPHERE_CONSTRAINT_GEODESIC_BALL) {
+            const double* ctr = K.centres + (int64_t)K.index[k] * dim;
+            const double s = (c > -1.0 && c < 1.0) ? 1.0 / __builtin_sqrt(1.0 - c * c) : 0.0;      // egrad = s centre
+            double a = 0.0;
+            for (int e = threadIdx.x; e < dim; e += 64) a = __builtin_fma(x[e], s * ctr[e], a);
+            a = wave_sum(a);
+            for (int e = threadIdx.x; e < dim; e += 64) gk[e] = s * ctr[e] - a * x[e];
+        } else {
+            const int j = K.index[k];
+            const double sgn = K.kind[k] == GABO_SPHERE_CONSTRAINT_COORD_LOWER ? 1.0 : -1.0;     // egrad = sgn e_j, <x, egrad> = sgn x[j]
+            const double a = sgn * x[j];
+            for (int e = threadIdx.x; e < dim; e += 64) gk[e] = (e == j ? sgn : 0.0) - a * x[e];
+        }
+    }
+}
+
+// the strict solver's verdict on a point (constrained_trust_regions.py:932-951): an equality off zero or an inequality below it
+static __device__ __forceinline__ bool sph_cons_infeasible(const double* __restrict__ x, int dim, const SphCons& K) {
+    bool bad = false;
+    for (int k = 0; k < K.n; ++k) {
+        double c;
+        const double v = sph_cons_value(x, dim, K, k, &c);
+        bad = bad || (k < K.neq ? v != 0.0 : !(v >= 0.0));
+    }
+    return bad;
+}
+
+__global__ __launch_bounds__(64) void sphere_constraints_kernel(const double* __restrict__ x, SphCons K, double* __restrict__ values,
+                                                                double* __restrict__ rgrads, int64_t R, int dim) {
+    const int64_t i = blockIdx.x;
+    sph_cons_eval(x + i * dim, dim, K, values + i * K.n, rgrads ? rgrads + i * dim : nullptr, R * dim);
+}
+
 __global__ __launch_bounds__(64) void sphere_acq_kernel(const double* __restrict__ x, SphAcq P, double* __restrict__ value,
                                                         double* __restrict__ grad, int64_t R) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
@@ -515,24 +586,29 @@ __global__ __launch_bounds__(64) void sphere_tr_update_kernel(double* __restrict
 // (the solve owns its restart from the first iteration to the last: nothing in the workspace has to survive the launch), known at compile time so that
 // their accesses are ds_read / ds_write and not flat loads (see spd_tr_solve_kernel).  Dynamic LDS: 7 n + 6 dim doubles, then n^2 + 2 n dim (the training points in both
 // layouts) + the workspace of ONE restart.
-static inline size_t sph_solve_lds(int64_t n, int dim, int64_t r, bool sym, bool* lat) {
+static inline size_t sph_solve_lds(int64_t n, int dim, int64_t r, bool sym, int C, bool* lat) {
     const size_t base = (size_t)(7 * n + 6 * dim) * sizeof(double);
-    const size_t extra = (size_t)(n * n + 2 * n * dim) * sizeof(double) + ((sph_layout(nullptr, 1, dim, 0).bytes + 15) & ~(size_t)15);
+    const size_t extra = (size_t)(n * n + 2 * n * dim) * sizeof(double) + ((sph_layout(nullptr, 1, dim, C).bytes + 15) & ~(size_t)15);
     *lat = sym && r <= 2048 && base + extra <= 56 * 1024;
     return base + (*lat ? extra : 0);
 }
 
-template <bool LAT>
+// CONS: the built-in constraints K are evaluated by the wave - at the iterate (values and gradients into the workspace, kept while x does
+// not move) and, strict, at the proposal.  !CONS ignores K: the unconstrained instantiations are those the kernel had before it knew constraints.
+template <bool LAT, bool CONS>
 __global__ __launch_bounds__(64) void sphere_tr_solve_kernel(double* __restrict__ x, double* __restrict__ fx, double* __restrict__ g,
                                                              double* __restrict__ ng, double* __restrict__ delta_tr,
                                                              uint8_t* __restrict__ active, int64_t* __restrict__ iters, SphAcq P,
                                                              void* wsbase, int64_t R, double theta, double kappa, int mininner,
                                                              int maxinner, double delta_bar, double rho_prime, double rho_regularization,
                                                              double mingradnorm, int64_t maxiter, int exact_hessian,
-                                                             double* __restrict__ rec, int64_t rec_cap) {
+                                                             double* __restrict__ rec, int64_t rec_cap, SphCons K) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     const int64_t i = blockIdx.x;
     if (active[i] == 0) return;
+    const int C = CONS ? K.n : 0;
+    const int neq = CONS ? K.neq : 0;
+    const double delta_cons = CONS ? K.delta_cons : 1e-6;
     SphAcq Ps = P;
     SphWs w;
     int64_t iw = i, Rw = R;
@@ -551,20 +627,27 @@ __global__ __launch_bounds__(64) void sphere_tr_solve_kernel(double* __restrict_
         Ps.train = tr;
         Ps.train_t = trt;
         double* wb = trt + P.n * P.dim;
-        w = sph_layout(wb, 1, P.dim, 0);
+        w = sph_layout(wb, 1, P.dim, C);
         for (size_t e = threadIdx.x; e < (w.bytes + 7) / 8; e += 64) wb[e] = 0.0;
         iw = 0;
         Rw = 1;
         __syncthreads();
     } else {
-        w = sph_layout(wsbase, R, P.dim, 0);
+        w = sph_layout(wsbase, R, P.dim, C);
     }
     bool x_unchanged = false;         // wave-uniform: the previous proposal of this launch was rejected
     int64_t rec_k = rec != nullptr ? iters[i] : 0;      // gabo_tr_solve_record: index of the outer iteration being recorded
     for (;;) {
-        sph_propose_body(x + i * P.dim, g + i * P.dim, delta_tr[i], nullptr, nullptr, Ps, w, iw, Rw, 0, 0, 1e-6, theta, kappa, mininner,
+        if constexpr (CONS) {
+            if (!x_unchanged) sph_cons_eval(x + i * P.dim, P.dim, K, w.fc + iw * C, w.gc + iw * P.dim, Rw * P.dim);
+        }
+        sph_propose_body(x + i * P.dim, g + i * P.dim, delta_tr[i], nullptr, nullptr, Ps, w, iw, Rw, C, neq, delta_cons, theta, kappa, mininner,
                          maxinner, dyn + 7 * P.n, dyn, exact_hessian, x_unchanged);
         __syncthreads();
+        bool inval = false;
+        if constexpr (CONS) {
+            if (K.strict) inval = sph_cons_infeasible(w.x_prop + iw * P.dim, P.dim, K);
+        }
         if (rec != nullptr && rec_k < rec_cap) {          // (the iterate, its radius and the stop reason of the tCG run that made the proposal)
             double* rr = rec + (rec_k * R + i) * (P.dim + 2);
             for (int e = threadIdx.x; e < P.dim; e += 64) rr[e] = x[i * P.dim + e];
@@ -575,7 +658,7 @@ __global__ __launch_bounds__(64) void sphere_tr_solve_kernel(double* __restrict_
         }
         ++rec_k;
         bool accepted = false;
-        const bool still = sph_update_body(x + i * P.dim, fx + i, g + i * P.dim, ng + i, delta_tr + i, iters + i, false, w, iw, P.dim, 0,
+        const bool still = sph_update_body(x + i * P.dim, fx + i, g + i * P.dim, ng + i, delta_tr + i, iters + i, inval, w, iw, P.dim, C,
                                            delta_bar, rho_prime, rho_regularization, mingradnorm, maxiter, &accepted);
         if (!still) break;
         x_unchanged = !accepted;
@@ -592,6 +675,28 @@ static int sph_acq_ok(const SphAcq* a) {
     if (a->kind != GABO_ACQ_EXPECTED_IMPROVEMENT && a->kind != GABO_ACQ_POSTERIOR_MEAN) return GABO_ERR_ARG;
     if (a->kind == GABO_ACQ_EXPECTED_IMPROVEMENT && (!a->linv || !a->linv_t)) return GABO_ERR_ARG;
     if ((size_t)(7 * a->n + 6 * a->dim) * sizeof(double) > 150 * 1024) return GABO_ERR_ARG;
+    return GABO_OK;
+}
+
+// the host arrays of a constraint set checked and packed into the kernel argument
+static int sph_cons_ok(int n, int neq, const int* kind, const int* index, const double* bound, const double* centres, int n_centres, int dim,
+                       int strict, double delta_cons, SphCons* K) {
+    if (n < 0 || n > kMaxCons || neq < 0 || neq > n || n_centres < 0) return GABO_ERR_ARG;
+    if (n > 0 && (!kind || !index || !bound)) return GABO_ERR_ARG;
+    *K = SphCons{};
+    K->n = n;
+    K->neq = neq;
+    K->strict = strict != 0;
+    K->delta_cons = delta_cons;
+    K->centres = centres;
+    for (int k = 0; k < n; ++k) {
+        const bool coord = kind[k] == GABO_SPHERE_CONSTRAINT_COORD_LOWER || kind[k] == GABO_SPHERE_CONSTRAINT_COORD_UPPER;
+        if (!coord && kind[k] != GABO_SPHERE_CONSTRAINT_GEODESIC_BALL) return GABO_ERR_ARG;
+        if (index[k] < 0 || index[k] >= (coord ? dim : n_centres) || (!coord && !centres)) return GABO_ERR_ARG;
+        K->kind[k] = kind[k];
+        K->index[k] = index[k];
+        K->bound[k] = bound[k];
+    }
     return GABO_OK;
 }
 
@@ -656,30 +761,62 @@ int gabo_sphere_tr_update(double* x, double* fx, double* grad, double* grad_norm
     return hipGetLastError() == hipSuccess ? GABO_OK : GABO_ERR_LAUNCH;
 }
 
-int gabo_sphere_tr_solve(double* x, double* fx, double* grad, double* grad_norm, double* trust_radius, uint8_t* active, int64_t* iters,
-                         const gabo_sphere_acq_params* acq, void* workspace, size_t workspace_bytes, int64_t r, double theta, double kappa,
-                         int mininner, int maxinner, int exact_hessian, double delta_bar, double rho_prime, double rho_regularization,
-                         double mingradnorm, int64_t maxiter, gabo_stream_t stream) {
+int gabo_sphere_constraints_eval(const double* x, int64_t r, int dim, int n_constraints, const int* kind, const int* index,
+                                 const double* bound, const double* centres, int n_centres, double* values, double* rgrads,
+                                 gabo_stream_t stream) {
+    if (dim < 2 || dim > 512) return GABO_ERR_DIM;
+    gabo::SphCons K;
+    int rc = gabo::sph_cons_ok(n_constraints, 0, kind, index, bound, centres, n_centres, dim, 0, 0.0, &K);
+    if (rc != GABO_OK) return rc;
+    if (r < 0 || r > 0x7fffffffLL) return GABO_ERR_ARG;
+    if (r == 0 || n_constraints == 0) return GABO_OK;
+    if (!x || !values) return GABO_ERR_ARG;
+    hipLaunchKernelGGL(gabo::sphere_constraints_kernel, dim3((unsigned)r), dim3(64), 0, (hipStream_t)stream, x, K, values, rgrads, r, dim);
+    return hipGetLastError() == hipSuccess ? GABO_OK : GABO_ERR_LAUNCH;
+}
+
+int gabo_sphere_tr_solve_lds_resident(const gabo_sphere_acq_params* acq, int64_t r, int n_constraints) {
+    if (gabo::sph_acq_ok(acq) != GABO_OK || r < 1 || r > 0x7fffffffLL || n_constraints < 0 || n_constraints > gabo::kMaxCons) return GABO_ERR_ARG;
+    bool lat = false;
+    gabo::sph_solve_lds(acq->n, acq->dim, r, acq->linv != nullptr && acq->linv == acq->linv_t, n_constraints, &lat);
+    return lat ? 1 : 0;
+}
+
+int gabo_sphere_tr_solve_constrained(double* x, double* fx, double* grad, double* grad_norm, double* trust_radius, uint8_t* active,
+                                     int64_t* iters, const gabo_sphere_acq_params* acq, void* workspace, size_t workspace_bytes, int64_t r,
+                                     double theta, double kappa, int mininner, int maxinner, int exact_hessian, double delta_bar,
+                                     double rho_prime, double rho_regularization, double mingradnorm, int64_t maxiter, int n_constraints,
+                                     int n_equalities, const int* kind, const int* index, const double* bound, const double* centres,
+                                     int n_centres, int strict, double delta_cons, gabo_stream_t stream) {
     double* rec = nullptr;
     int64_t rec_cap = 0;
     gabo::tr_record_take(&rec, &rec_cap);                 // gabo_tr_solve_record (spd_tr.hip): consumed by this call whether it launches or not
     int rc = gabo::sph_acq_ok(acq);
     if (rc != GABO_OK) return rc;
+    gabo::SphCons K;
+    rc = gabo::sph_cons_ok(n_constraints, n_equalities, kind, index, bound, centres, n_centres, acq->dim, strict, delta_cons, &K);
+    if (rc != GABO_OK) return rc;
     if (r < 0 || r > 0x7fffffffLL || maxinner < 1 || maxiter < 1) return GABO_ERR_ARG;
     if (r == 0) return GABO_OK;
     if (!x || !fx || !grad || !grad_norm || !trust_radius || !active || !iters || !workspace) return GABO_ERR_ARG;
-    if (workspace_bytes < gabo_sphere_tr_workspace_bytes(r, acq->dim, 0)) return GABO_ERR_ARG;
+    if (workspace_bytes < gabo_sphere_tr_workspace_bytes(r, acq->dim, n_constraints)) return GABO_ERR_ARG;
     bool lat = false;
-    const size_t lds = gabo::sph_solve_lds(acq->n, acq->dim, r, acq->linv != nullptr && acq->linv == acq->linv_t, &lat);
-    if (lat)
-        hipLaunchKernelGGL(gabo::sphere_tr_solve_kernel<true>, dim3((unsigned)r), dim3(64), lds, (hipStream_t)stream, x, fx, grad, grad_norm,
-                           trust_radius, active, iters, *acq, workspace, r, theta, kappa, mininner, maxinner, delta_bar, rho_prime,
-                           rho_regularization, mingradnorm, maxiter, exact_hessian, rec, rec_cap);
-    else
-        hipLaunchKernelGGL(gabo::sphere_tr_solve_kernel<false>, dim3((unsigned)r), dim3(64), lds, (hipStream_t)stream, x, fx, grad, grad_norm,
-                           trust_radius, active, iters, *acq, workspace, r, theta, kappa, mininner, maxinner, delta_bar, rho_prime,
-                           rho_regularization, mingradnorm, maxiter, exact_hessian, rec, rec_cap);
+    const size_t lds = gabo::sph_solve_lds(acq->n, acq->dim, r, acq->linv != nullptr && acq->linv == acq->linv_t, n_constraints, &lat);
+    auto kernel = n_constraints > 0 ? (lat ? gabo::sphere_tr_solve_kernel<true, true> : gabo::sphere_tr_solve_kernel<false, true>)
+                                    : (lat ? gabo::sphere_tr_solve_kernel<true, false> : gabo::sphere_tr_solve_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)r), dim3(64), lds, (hipStream_t)stream, x, fx, grad, grad_norm, trust_radius, active, iters, *acq,
+                       workspace, r, theta, kappa, mininner, maxinner, delta_bar, rho_prime, rho_regularization, mingradnorm, maxiter,
+                       exact_hessian, rec, rec_cap, K);
     return hipGetLastError() == hipSuccess ? GABO_OK : GABO_ERR_LAUNCH;
+}
+
+int gabo_sphere_tr_solve(double* x, double* fx, double* grad, double* grad_norm, double* trust_radius, uint8_t* active, int64_t* iters,
+                         const gabo_sphere_acq_params* acq, void* workspace, size_t workspace_bytes, int64_t r, double theta, double kappa,
+                         int mininner, int maxinner, int exact_hessian, double delta_bar, double rho_prime, double rho_regularization,
+                         double mingradnorm, int64_t maxiter, gabo_stream_t stream) {
+    return gabo_sphere_tr_solve_constrained(x, fx, grad, grad_norm, trust_radius, active, iters, acq, workspace, workspace_bytes, r, theta, kappa,
+                                            mininner, maxinner, exact_hessian, delta_bar, rho_prime, rho_regularization, mingradnorm, maxiter, 0,
+                                            0, nullptr, nullptr, nullptr, nullptr, 0, 0, 1e-6, stream);
 }
 
 }  // extern "C"

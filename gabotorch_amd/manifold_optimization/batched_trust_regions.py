@@ -23,8 +23,8 @@ def _library():
 
 
 def _library_constraint_quick(con):
-    """this package's own eigenvalue constraints bound by functools.partial: batch-safe by construction (and possibly under graph capture,
-    where a host-side comparison could not run)"""
+    """this package's own eigenvalue and sphere constraints bound by functools.partial: batch-safe by construction (and possibly under graph
+    capture, where a host-side comparison could not run)"""
     try:
         from .manifold_optimize import _library_constraint
         return bool(_library_constraint(con))
@@ -409,6 +409,19 @@ class BatchedTrustRegions:
         return [b[0] == _lib.GABO_CONSTRAINT_MAX_EIGENVALUE_NESTED for b in info], [b[1] for b in info], memo[1]
 
     @staticmethod
+    def _sphere_group(problem, x, constraints):
+        """(kinds, indices, bounds, centres) when x is a batch of points of the sphere on the device and EVERY constraint is one of the
+        library's sphere constraints (sphere_constraints_utils_torch.builtin_sphere_group): one launch of gabo_sphere_constraints_eval
+        then serves them all, values and Riemannian gradients, no Python call per constraint and no autograd graph.  None otherwise."""
+        if not constraints or not torch.is_tensor(x) or not x.is_cuda or x.dim() != 2 or x.dtype != torch.float64:
+            return None
+        from ..manifolds import Sphere
+        if problem is not None and not isinstance(getattr(problem, "manifold", None), Sphere):
+            return None
+        from ..Riemannian_utils.sphere_constraints_utils_torch import builtin_sphere_group
+        return builtin_sphere_group(constraints, x.shape[-1], x.device)
+
+    @staticmethod
     def _call_constraint(con, x):
         """Values (R,) of one user constraint at the R points x.  The reference's convention is a callable of ONE point (`x[1] - yc`,
         gabo_sphere_equality_constraints.py:106-107); a callable written for a batch (`x[..., 1] - yc`) saves R - 1 calls.  The batched call is
@@ -455,6 +468,11 @@ class BatchedTrustRegions:
             vals = [(b - lam[:, 0]) if mx else (lam[:, 1] - b) for mx, b in zip(is_max, bounds)]
             grads = [problem.manifold.egrad2rgrad(x, (-grad[:, 0]) if mx else grad[:, 1]) for mx in is_max]
             return torch.stack(vals, dim=1).to(x.dtype), grads
+        group = BatchedTrustRegions._sphere_group(problem, x, constraints)
+        if group is not None:
+            from .. import ops
+            vals, grads = ops.sphere_constraints_eval(x.detach(), *group)
+            return vals, list(grads.unbind(0))
         vals, grads = [], []
         for con in constraints:
             xx = x.detach().clone().requires_grad_(True)
@@ -476,6 +494,10 @@ class BatchedTrustRegions:
             is_max, bounds, (w, x0, p) = group
             lam = ops.nested_spd_extreme_eigenvalues(x.detach(), w, p, x0)
             return torch.stack([(b - lam[:, 0]) if mx else (lam[:, 1] - b) for mx, b in zip(is_max, bounds)], dim=1).to(x.dtype)
+        group = BatchedTrustRegions._sphere_group(None, x, constraints)
+        if group is not None:
+            from .. import ops
+            return ops.sphere_constraints_eval(x.detach(), *group, want_grad=False)
         vals = []
         with torch.no_grad():
             for con in constraints:
@@ -604,18 +626,24 @@ class BatchedTrustRegions:
         # (the library says which of its iteration kernels exist for this surrogate: e.g. no propose / update pair for the log-Euclidean
         # surrogate at d = 8, csrc/spd_tr_le_hi.hip, and no generic-workspace single launch for it at d = 7, 8, csrc/spd_tr_body.hpp)
         propose_ok = bool(fused_kernels and (sphere or _library().gabo_spd_tr_propose_supported(int(fused.mode) | int(fused.metric), d)))
-        if fused_kernels:
+        if fused_kernels and sphere:
+            # no constraint needs a host callable: none, or the library's coordinate bounds and geodesic balls built with functools.partial,
+            # equalities among them (csrc/sphere_tr.hip); builtins = (kinds, indices, bounds, centres)
+            builtins = self._sphere_group(problem, x, cons) if ncons else ([], [], [], None)
+            solve_ok = builtins is not None
+        elif fused_kernels:
             from ..Riemannian_utils.spd_constraints_utils_torch import builtin_constraint, builtin_lift
             builtins = [builtin_constraint(c) for c in cons]
             # no constraint needs a host callable (none, or eigenvalue bounds built with functools.partial as in the reference examples)
-            solve_ok = (ncons == 0) if sphere else (d <= 8 and neq == 0 and all(b is not None for b in builtins))
-            lift = builtin_lift(builtins) if (solve_ok and not sphere) else None      # the nested kinds' mapping (one for all of them)
+            solve_ok = d <= 8 and neq == 0 and all(b is not None for b in builtins)
+            lift = builtin_lift(builtins) if solve_ok else None      # the nested kinds' mapping (one for all of them)
             solve_ok = solve_ok and lift is not False
-            if solve_ok and not sphere:
+            if solve_ok:
                 # (the library's own word: e.g. no single-launch form of the log-Euclidean surrogate at d = 7, 8 beyond what its LDS holds)
                 import ctypes
                 solve_ok = bool(_library().gabo_spd_tr_solve_supported(ctypes.byref(fused.acq_params()), R, d, ncons,
                                                                        0 if lift is None else int(lift[0].shape[0])))
+        if fused_kernels:
             one_launch = bool(solve_ok and getattr(problem, "device_solve", True) and self.maxtime >= 1000)
         args = (problem, x, cons, neq, mininner, maxinner, Delta_bar, Delta0, Delta_cons)
         if one_launch:
@@ -632,19 +660,24 @@ class BatchedTrustRegions:
         return ops.SpdTr(R, d, ncons, fused.acq_params(), fused.train.shape[0], x.device)
 
     def _single_launch_solve(self, problem, x, cons, neq, mininner, maxinner, Delta_bar, Delta0, Delta_cons, builtins, lift):
-        """gabo_spd_tr_solve / gabo_sphere_tr_solve: every wave iterates its restart to the end"""
+        """gabo_spd_tr_solve / gabo_sphere_tr_solve[_constrained]: every wave iterates its restart to the end"""
         from .. import ops
         R, d, dt, dev = x.shape[0], x.shape[-1], x.dtype, x.device
         sphere = problem.fused.family == "sphere"
         S = _RestartState(problem, x, Delta0)
         TR = self._iteration_kernels(problem, x, len(cons))
-        extra = {} if sphere else {"lift": lift}
+        if sphere:
+            kinds, indices, bounds, centres = builtins
+            extra = {"indices": indices, "centres": centres, "n_equalities": neq}
+        else:
+            kinds, bounds = [b[0] for b in builtins], [b[1] for b in builtins]
+            extra = {"lift": lift}
         if self.trace is not None:
             # the launch writes its own record (gabo_tr_solve_record): iterate, radius, tCG stop reason per outer iteration
             L = d if sphere else d * d
             extra["record"] = torch.full((int(min(self.maxiter, 1 << 14)), R, L + 2), float("nan"), dtype=dt, device=dev)
-        TR.solve(S.x, S.fx, S.g, S.ng, S.Delta, S.active.view(torch.uint8), S.iters, [b[0] for b in builtins], [b[1] for b in builtins],
-                 bool(cons and self.strict_constraints), Delta_cons, self.theta, self.kappa, mininner, maxinner, Delta_bar, self.rho_prime,
+        TR.solve(S.x, S.fx, S.g, S.ng, S.Delta, S.active.view(torch.uint8), S.iters, kinds, bounds, bool(cons and self.strict_constraints),
+                 Delta_cons, self.theta, self.kappa, mininner, maxinner, Delta_bar, self.rho_prime,
                  self.rho_regularization, self.mingradnorm, self.maxiter, **extra)
         if hasattr(TR, "status"):
             ops._raise_if_not_spd(TR.status, "gabo_spd_tr_solve")       # (when error checking is on: one read-back per solve)
@@ -656,7 +689,10 @@ class BatchedTrustRegions:
                 self.trace.append({"x": rec[kk, :, :L].reshape(x.shape).clone(), "Delta": rec[kk, :, L].clone(), "active": ran,
                                    "stop_inner": torch.where(ran, rec[kk, :, L + 1], torch.full_like(rec[kk, :, L], -1.0)).long()})
         ops.check_deferred()
-        self._set_log(problem, k, S.iters, S.fx, S.ng, S.Delta, S.time0, one_launch_solve=True)
+        plan = {"one_launch_solve": True}
+        if sphere:
+            plan["lds_resident"] = TR.lds_resident()       # (which instantiation of the kernel ran: gabo_sphere_tr_solve_lds_resident)
+        self._set_log(problem, k, S.iters, S.fx, S.ng, S.Delta, S.time0, **plan)
         return S.x
 
     def _propose_update_launches(self, problem, x, cons, neq, mininner, maxinner, Delta_bar, Delta0, Delta_cons):

@@ -1757,18 +1757,66 @@ class SphereTr:
                                                       self.any_active.data_ptr(), _stream_ptr(self.dev)), "gabo_sphere_tr_update")
 
     def solve(self, x, fx, g, ng, Delta, active, iters, kinds, bounds, strict, delta_cons, theta, kappa, mininner, maxinner, delta_bar,
-              rho_prime, rho_regularization, mingradnorm, maxiter, record=None):
-        _require(self.dev, x=x, fx=fx, g=g, ng=ng, Delta=Delta, active=active, iters=iters, record=record)
-        assert not kinds, "the sphere has no built-in constraints"
+              rho_prime, rho_regularization, mingradnorm, maxiter, record=None, indices=(), centres=None, n_equalities=0):
+        """The whole solve in one launch, without constraints or with the library's own sphere constraints (`kinds` / `indices` / `bounds`
+        and the balls' `centres` as sphere_constraints_utils_torch.builtin_sphere_group packs them, the `n_equalities` equalities first).
+        record: (K, r, dim + 2) tensor pre-filled with NaN -> per-iteration record of the launch (gabo_tr_solve_record)."""
+        _require(self.dev, x=x, fx=fx, g=g, ng=ng, Delta=Delta, active=active, iters=iters, record=record, centres=centres)
+        import ctypes
+        nc = len(kinds)
+        if nc != self.c or len(indices) != nc or len(bounds) != nc:
+            raise ValueError(f"{nc} constraint kinds, {len(indices)} indices and {len(bounds)} bounds for a workspace of {self.c} constraints")
+        ck = (ctypes.c_int * max(nc, 1))(*kinds)
+        ci = (ctypes.c_int * max(nc, 1))(*indices)
+        cb = (ctypes.c_double * max(nc, 1))(*bounds)
+        if centres is not None and (centres.dim() != 2 or centres.shape[1] != self.d):
+            raise ValueError("centres: n_centres x dim")
         with _on(self.dev):
             if record is not None:                     # (K, r, dim + 2), pre-filled with NaN: gabo_tr_solve_record
                 assert tuple(record.shape[1:]) == (self.r, self.d + 2)
                 _lib.check(self.lib.gabo_tr_solve_record(record.data_ptr(), int(record.shape[0])), "gabo_tr_solve_record")
-            _lib.check(self.lib.gabo_sphere_tr_solve(x.data_ptr(), fx.data_ptr(), g.data_ptr(), ng.data_ptr(), Delta.data_ptr(),
-                                                     active.data_ptr(), iters.data_ptr(), self.acq_ref, self.ws.data_ptr(), self.wsb, self.r,
-                                                     float(theta), float(kappa), int(mininner), int(maxinner), self.exact, float(delta_bar),
-                                                     float(rho_prime), float(rho_regularization), float(mingradnorm), int(maxiter),
-                                                     _stream_ptr(self.dev)), "gabo_sphere_tr_solve")
+            _lib.check(self.lib.gabo_sphere_tr_solve_constrained(
+                x.data_ptr(), fx.data_ptr(), g.data_ptr(), ng.data_ptr(), Delta.data_ptr(), active.data_ptr(), iters.data_ptr(), self.acq_ref,
+                self.ws.data_ptr(), self.wsb, self.r, float(theta), float(kappa), int(mininner), int(maxinner), self.exact, float(delta_bar),
+                float(rho_prime), float(rho_regularization), float(mingradnorm), int(maxiter), nc, int(n_equalities), ck, ci, cb,
+                None if centres is None else centres.data_ptr(), 0 if centres is None else int(centres.shape[0]), 1 if strict else 0,
+                float(delta_cons), _stream_ptr(self.dev)), "gabo_sphere_tr_solve_constrained")
+
+    def lds_resident(self):
+        """whether solve() keeps the surrogate and the restart's workspace in LDS (gabo_sphere_tr_solve_lds_resident)"""
+        rc = self.lib.gabo_sphere_tr_solve_lds_resident(self.acq_ref, self.r, self.c)
+        if rc < 0:
+            _lib.check(rc, "gabo_sphere_tr_solve_lds_resident")
+        return bool(rc)
+
+
+def sphere_constraints_eval(x, kinds, indices, bounds, centres=None, want_grad=True):
+    """Values (R x C) and, want_grad, Riemannian gradients (C x R x dim) of the library's own sphere constraints at the R points x (R x dim)
+    in one launch (gabo_sphere_constraints_eval); the arguments as sphere_constraints_utils_torch.builtin_sphere_group packs them."""
+    import ctypes
+    lib = _lib.load()
+    dev = _device_for(x)
+    xx = _prep(x, dev).contiguous()
+    if xx.dim() != 2:
+        raise ValueError("x: R x dim")
+    r, dim, nc = xx.shape[0], xx.shape[1], len(kinds)
+    if len(indices) != nc or len(bounds) != nc:
+        raise ValueError("kinds, indices and bounds: one entry per constraint")
+    if centres is not None:
+        centres = _prep(centres, dev).contiguous()
+        if centres.dim() != 2 or centres.shape[1] != dim:
+            raise ValueError("centres: n_centres x dim")
+    values = torch.empty(r, nc, dtype=torch.float64, device=dev)
+    grads = torch.empty(nc, r, dim, dtype=torch.float64, device=dev) if want_grad else None
+    ck = (ctypes.c_int * max(nc, 1))(*kinds)
+    ci = (ctypes.c_int * max(nc, 1))(*indices)
+    cb = (ctypes.c_double * max(nc, 1))(*bounds)
+    with _on(dev):
+        _lib.check(lib.gabo_sphere_constraints_eval(xx.data_ptr(), r, dim, nc, ck, ci, cb, None if centres is None else centres.data_ptr(),
+                                                    0 if centres is None else int(centres.shape[0]), values.data_ptr(),
+                                                    None if grads is None else grads.data_ptr(), _stream_ptr(dev)),
+                   "gabo_sphere_constraints_eval")
+    return (values, grads) if want_grad else values
 
 
 def sphere_manifold_op(op, x, u, v=None, w=None):

@@ -596,7 +596,9 @@ int gabo_spd_sweep_solve_rows(const gabo_spd_sweep_config* cfg, const int64_t* p
  * Hessian (approximate_hessian.py:11-62) on pymanopt's Sphere geometry, one wave per restart.  State arrays: x, grad r x dim
  * (grad = Riemannian gradient), fx, grad_norm, trust_radius r; active r bytes; iters r int64; cons_grads n_constraints x r x dim
  * (Riemannian gradients, equalities first), cons_values r x n_constraints.  gabo_sphere_tr_solve runs the whole solve in one launch
- * when there are no constraints (constraints on the sphere are user callables).  exact_hessian != 0: the tCG uses the exact
+ * when there are no constraints, gabo_sphere_tr_solve_constrained when every constraint is one of the library's own
+ * (GABO_SPHERE_CONSTRAINT_*: the functions of Riemannian_utils/sphere_constraints_utils_torch.py, evaluated by the wave); any other
+ * constraint is a user callable evaluated between gabo_sphere_tr_propose and gabo_sphere_tr_update.  exact_hessian != 0: the tCG uses the exact
  * Riemannian Hessian-vector product (closed form of the double backward the reference runs through its sphere kernel,
  * pymanopt_addons/tools/autodiff/_pytorch.py:103-116; the stock TrustRegions of examples/gabo_sphere.py:151) instead of
  * get_hessianfd. */
@@ -621,7 +623,7 @@ size_t gabo_sphere_tr_workspace_bytes(int64_t r, int dim, int n_constraints);
  * per-iteration record of the solver reads between gabo_sphere_tr_propose and gabo_sphere_tr_update (robust_trust_regions.py:190 `srstr`) */
 size_t gabo_sphere_tr_stop_offset(int64_t r, int dim, int n_constraints);
 /* Per-iteration record of the single-launch solves - what the reference's solvers keep in their optlog (robust_trust_regions.py:300-340:
- * iterate, radius, `srstr`) and tests/golden/tr_traces.npz holds for them.  The NEXT call of gabo_spd_tr_solve or gabo_sphere_tr_solve of
+ * iterate, radius, `srstr`) and tests/golden/tr_traces.npz holds for them.  The NEXT call of gabo_spd_tr_solve or gabo_sphere_tr_solve[_constrained] of
  * this process (one pending buffer; not thread-safe: a parity / debugging facility) writes, for outer iteration k < max_iterations of restart
  * i, buffer[(k * r + i) * (L + 2) + ...] = the iterate (L = d * d doubles, or dim for the sphere), the trust radius and the stop reason of the
  * truncated-CG run that made the proposal judged in that iteration.  buffer: device memory of max_iterations * r * (L + 2) doubles that the
@@ -639,6 +641,32 @@ int gabo_sphere_tr_solve(double* x, double* fx, double* grad, double* grad_norm,
                          const gabo_sphere_acq_params* acq, void* workspace, size_t workspace_bytes, int64_t r, double theta, double kappa,
                          int mininner, int maxinner, int exact_hessian, double delta_bar, double rho_prime, double rho_regularization,
                          double mingradnorm, int64_t maxiter, gabo_stream_t stream);
+
+/* The library's own constraints on the sphere (equalities or inequalities c(x) >= 0): coordinate bounds (gabo_sphere_bound_constraints.py:94-121,
+ * the great circle of gabo_sphere_equality_constraints.py:106-107 as an equality) and the geodesic ball (gabo_sphere_inequality_constraints.py). */
+#define GABO_SPHERE_CONSTRAINT_COORD_LOWER   0   /* x[index] - bound                                   */
+#define GABO_SPHERE_CONSTRAINT_COORD_UPPER   1   /* bound - x[index]                                   */
+#define GABO_SPHERE_CONSTRAINT_GEODESIC_BALL 2   /* bound - acos(clip(<x, centres[index]>, -1, 1))     */
+
+/* values r x C, rgrads C x r x dim (NULL: values only). kind/index/bound: host arrays (as gabo_spd_tr_solve's).  centres: n_centres x dim on the
+ * device.  The ball's gradient is zero where |<x, centre>| >= 1.  At most 8 constraints. */
+int gabo_sphere_constraints_eval(const double* x, int64_t r, int dim, int n_constraints, const int* kind, const int* index,
+                                 const double* bound, const double* centres, int n_centres, double* values, double* rgrads,
+                                 gabo_stream_t stream);
+
+/* gabo_sphere_tr_solve with the constraints evaluated by the wave: equalities first (n_equalities of them), strict != 0 rejects
+ * infeasible proposals (an equality off zero or an inequality below it: constrained_trust_regions.py:932-951).  The workspace is that of
+ * gabo_sphere_tr_workspace_bytes(r, dim, n_constraints). */
+int gabo_sphere_tr_solve_constrained(double* x, double* fx, double* grad, double* grad_norm, double* trust_radius, uint8_t* active,
+                                     int64_t* iters, const gabo_sphere_acq_params* acq, void* workspace, size_t workspace_bytes, int64_t r,
+                                     double theta, double kappa, int mininner, int maxinner, int exact_hessian, double delta_bar,
+                                     double rho_prime, double rho_regularization, double mingradnorm, int64_t maxiter, int n_constraints,
+                                     int n_equalities, const int* kind, const int* index, const double* bound, const double* centres,
+                                     int n_centres, int strict, double delta_cons, gabo_stream_t stream);
+
+/* 1 when that launch keeps A, the training points and the restart's workspace in LDS (the LAT instantiation), 0 when it runs from the
+ * caller's workspace, <0 on bad arguments: for tests and tools to know which instantiation they exercised. */
+int gabo_sphere_tr_solve_lds_resident(const gabo_sphere_acq_params* acq, int64_t r, int n_constraints);
 
 /* The sphere counterpart, as two host calls around the caller's selection heuristic (score, then solve): one multi-start acquisition sweep of the reference's gabo_sphere examples
  * (examples/bo_sphere/benchmark_examples/gabo_sphere.py:151-175: stock TrustRegions, no constraints; manifold_optimize.py:36-321) as two host
