@@ -56,3 +56,33 @@ def spd_sample(self):
     d = self.min_eig * np.ones(1) + (self.max_eig - self.min_eig) * np.random.rand(self._n)
     u, _ = np.linalg.qr(np.random.randn(self._n, self._n))
     return np.dot(u, np.dot(np.diag(d), u.T))
+
+
+def parallel_transport_operator(S1, S2):
+    """(S2 S1^-1)^(1/2)   (spd_utils.py:200-213), as L1 sqrtm(L1^-1 S2 L1^-T) L1^-1 with L1 = chol(S1): S2 S1^-1 is similar, through L1, to the SPD matrix
+    in the middle, whose square root is one GABO_SPD_SQRTM launch.  Real by construction (the reference's fractional_matrix_power may hand back a
+    complex dtype with zero imaginary part).  P S1 P^T = S2."""
+    S1, S2 = np.asarray(S1, dtype=float), np.asarray(S2, dtype=float)
+    L = np.linalg.cholesky(S1)
+    Li = np.linalg.inv(L)
+    M = Li @ S2 @ Li.T
+    R = ops.spd_manifold_op(_lib.GABO_SPD_SQRTM, torch.as_tensor(0.5 * (M + M.T))).numpy()
+    return L @ R @ Li
+
+
+def parallel_transport_operator_mandel_vector(s1, s2):
+    """(spd_utils.py:216-232)"""
+    return parallel_transport_operator(vector_to_symmetric_matrix_mandel(s1), vector_to_symmetric_matrix_mandel(s2))
+
+
+def mean(data, nb_iter=10):
+    """Frechet mean of the N x d x d SPD matrices `data`, started at data[0]   (spd_utils.py:235-259): one enqueued chain of launches
+    (ops.spd_frechet_mean) instead of 2 N nb_iter host eigen-decompositions."""
+    data = np.asarray(data, dtype=float)
+    return vector_to_symmetric_matrix_mandel(ops.spd_frechet_mean(torch.as_tensor(symmetric_matrix_to_vector_mandel(data)), iters=nb_iter).numpy())
+
+
+def mean_mandel_vector(data, nb_iter=10):
+    """The same for Mandel vectors in the COLUMNS of `data` (d_vec x N) -> (d_vec,)   (spd_utils.py:262-287)"""
+    data = np.asarray(data, dtype=float)
+    return ops.spd_frechet_mean(torch.as_tensor(np.ascontiguousarray(data.T)), iters=nb_iter).numpy()

@@ -46,3 +46,22 @@ def rotation_from_sphere_points(x, y):
     s = np.sqrt((1.0 - t) * (1.0 + t))
     ye = np.outer(y, e)
     return np.eye(x.size) + s * (ye - ye.T) + (t - 1.0) * (np.outer(y, y) + np.outer(e, e))
+
+
+def parallel_transport_operator(x1, x2):
+    """The dim x dim operator that carries tangent vectors at x1 to x2 along their geodesic (sphere_utils.py:93-123), with v = Log_x1(x2) / |Log_x1(x2)|
+    from GABO_SPH_LOG:  -x1 sin|u| v^T + v cos|u| v^T + I - v v^T;  the identity when sum(x1 - x2) == 0, the reference's own shortcut (:107)."""
+    x1, x2 = np.asarray(x1, dtype=float), np.asarray(x2, dtype=float)
+    if np.sum(x1 - x2) == 0.:
+        return np.eye(x1.shape[0])
+    x1 = x1.reshape(-1, 1)
+    u = logmap(x2.reshape(-1), x1.reshape(-1))
+    nu = np.sqrt(np.sum(u * u, axis=0))
+    v = u / nu
+    return np.dot(-x1 * np.sin(nu), v.T) + np.dot(v * np.cos(nu), v.T) + np.eye(u.shape[0]) - np.dot(v, v.T)
+
+
+def karcher_mean_sphere(data, nb_iter=10):
+    """Karcher mean of the unit vectors in the columns of `data` (dim x N), started at data[:, 0] -> (dim, 1)   (sphere_utils.py:126-149)"""
+    data = np.asarray(data, dtype=float)
+    return ops.sphere_karcher_mean(torch.as_tensor(np.ascontiguousarray(data.T)), iters=nb_iter).numpy()[:, None]

@@ -164,6 +164,10 @@ SIGNATURES = {
     "gabo_spd_logm_mandel_backward": (_I, [_P, _P, _P, _I64, _I, _P]),
     "gabo_frobenius_backward": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _I64, _I64, _I64, _I64, _I64, _D, _I, _D, _P]),
     "gabo_sphere_manifold_op": (_I, [_I, _P, _P, _P, _P, _P, _I64, _I, _P]),
+    "gabo_spd_frechet_mean_workspace_bytes": (_SZ, [_I64, _I64, _I]),
+    "gabo_spd_frechet_mean": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I, _I, _P, _SZ, _P, _P]),
+    "gabo_sphere_karcher_mean_workspace_bytes": (_SZ, [_I64, _I64, _I]),
+    "gabo_sphere_karcher_mean": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I, _I, _P, _SZ, _P]),
     "gabo_mandel_to_matrix": (_I, [_P, _P, _I64, _I, _P]),
     "gabo_matrix_to_mandel": (_I, [_P, _P, _I64, _I, _P]),
     "gabo_nested_spd_reconstruction_workspace_bytes": (_SZ, [_I64, _I64, _I, _I]),

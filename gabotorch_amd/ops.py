@@ -1836,3 +1836,147 @@ def sphere_manifold_op(op, x, u, v=None, w=None):
         _lib.check(lib.gabo_sphere_manifold_op(int(op), ptr(X), ptr(U), ptr(V), ptr(W), out.data_ptr(), n, dim, _stream_ptr(dev)),
                    "gabo_sphere_manifold_op")
     return _out(out, out_device)
+
+
+# ------------------------------------------------------------------------------------------ Frechet / Karcher means
+GABO_SPD_MEAN_FUSED_MAX_DIM = 10          # the fused kernels of csrc/riemannian_mean.hip; above: the composed device path
+
+
+def _mean_args(x, weights, start, tail, dev):
+    """(..., N, tail) points with optional (..., N) weights and (..., tail) start -> contiguous (B, N, tail), (B, N) | None, (B, tail) | None"""
+    xs = _prep(torch.as_tensor(x), dev)
+    if xs.dim() < 2 or xs.shape[-2] < 1:
+        raise RuntimeError(f"a mean needs (..., N, {tail}) points with N >= 1, got {tuple(xs.shape)}")
+    bshape = xs.shape[:-2]
+    n = xs.shape[-2]
+    xs = xs.reshape(-1, n, xs.shape[-1]).contiguous()
+    w = s = None
+    if weights is not None:
+        w = _prep(torch.as_tensor(weights), dev)
+        if w.shape != bshape + (n,):
+            raise RuntimeError(f"weights {tuple(w.shape)} do not match the points {tuple(bshape + (n,))}")
+        w = w.reshape(-1, n).contiguous()
+    if start is not None:
+        s = _prep(torch.as_tensor(start), dev)
+        if s.shape != bshape + (xs.shape[-1],):
+            raise RuntimeError(f"start {tuple(s.shape)} does not match the points {tuple(bshape + (xs.shape[-1],))}")
+        s = s.reshape(-1, xs.shape[-1]).contiguous()
+    return xs, w, s, bshape
+
+
+def _spd_mean_message(nb, n):
+    def message(st):
+        if st[1] >= nb * n:
+            return f"gabo_spd_frechet_mean: the start point / an iterate of set #{st[1] - nb * n} is not positive definite (Cholesky pivot <= 0)"
+        return f"gabo_spd_frechet_mean: input matrix #{st[1]} is not positive definite (Cholesky pivot <= 0)"
+    return message
+
+
+def _spd_frechet_mean_composed(xs, w, s, iters, d):
+    """The mean from the library's batched launches: whiten with torch, one logm launch over the N matrices, a weighted sum, one expm launch, the
+    congruence - per iteration, nothing read back.  Serves 11 <= d <= GABO_SPD_MAX_DIM and is the second device implementation the fused kernels
+    are compared with.  Returns (mean, residuals, status): a status word of the ring (taken after the inner launches have taken theirs), written on
+    the device as gabo_spd_frechet_mean writes it - {GABO_ERR_NOT_SPD, index of the
+    first data matrix that is not positive definite (a failed Cholesky pivot or a NaN entry), or B N + the set whose start point / iterate failed}."""
+    nb, n = xs.shape[:2]
+    X = mandel_to_matrix(xs)                                                     # (B, N, d, d)
+    m = X[:, 0] if s is None else mandel_to_matrix(s)
+    wn = torch.full((nb, n), 1.0 / n, dtype=torch.float64, device=xs.device) if w is None else w / w.sum(-1, keepdim=True)
+    resid = torch.empty(nb, iters, dtype=torch.float64, device=xs.device)
+    bad_x = ((torch.linalg.cholesky_ex(X).info != 0) | torch.isnan(xs).any(-1)).reshape(-1)
+    bad_m = torch.zeros(nb, dtype=torch.bool, device=xs.device)
+    for it in range(iters + 1):
+        L, info = torch.linalg.cholesky_ex(m)                                   # (info stays on the device)
+        bad_m |= (info != 0) | torch.isnan(m).any(-1).any(-1)
+        if it == iters:
+            break
+        Y = torch.linalg.solve_triangular(L[:, None], X, upper=False)           # L^-1 X
+        M = torch.linalg.solve_triangular(L[:, None], Y.transpose(-1, -2), upper=False)     # L^-1 (L^-1 X)^T = L^-1 X L^-T
+        M = 0.5 * (M + M.transpose(-1, -2))
+        logs = spd_manifold_op(_lib.GABO_SPD_LOGM, M)
+        # (a point of weight 0 is skipped, as in the fused kernels: its logarithm - NaN included - stays out of the sum)
+        S = torch.where((wn != 0)[:, :, None, None], wn[:, :, None, None] * logs, torch.zeros((), dtype=torch.float64, device=xs.device)).sum(1)
+        resid[:, it] = torch.linalg.matrix_norm(S)
+        E = spd_manifold_op(_lib.GABO_SPD_EXPM, S)
+        m = torch.bmm(torch.bmm(L, E), L.transpose(-1, -2))
+        m = 0.5 * (m + m.transpose(-1, -2))
+    bad = torch.cat([bad_x, bad_m])
+    first = bad.to(torch.int32).argmax().to(torch.int32)
+    code = torch.where(bad.any(), torch.full_like(first, _lib.GABO_ERR_NOT_SPD), torch.zeros_like(first))
+    mean = matrix_to_mandel(m)
+    status = _status_word(xs.device)
+    status.copy_(torch.stack([code, torch.where(bad.any(), first, torch.zeros_like(first))]))
+    return mean, resid, status
+
+
+def spd_frechet_mean(x_mandel, weights=None, iters=10, start=None, return_residual=False, fused=None):
+    """Frechet mean under the affine-invariant metric of (N, d_vec) or (..., N, d_vec) Mandel vectors -> (d_vec,) or (..., d_vec), on the input's
+    device (the reference's `mean` / `mean_mandel_vector`, spd_utils.py:235-287, for one or many sets).  weights (..., N): non-negative, normalised
+    inside; start (..., d_vec): default the set's first point.  return_residual: also (..., iters), the norm of the mean tangent each iteration
+    started from.  fused=None: the fused kernels for d <= 10, the composed device path for 11 <= d <= 32; fused=False forces the composed path."""
+    lib = _lib.load()
+    first = torch.as_tensor(x_mandel)
+    out_device = first.device
+    dev = _device_for(*[torch.as_tensor(t_) for t_ in (x_mandel, weights, start) if t_ is not None])
+    iters = int(iters)
+    if iters < 0:
+        raise RuntimeError("iters must be >= 0")
+    xs, w, s, bshape = _mean_args(x_mandel, weights, start, "d_vec", dev)
+    d = _mandel_dim(xs.shape[-1])
+    if d < 2 or d > _lib.GABO_SPD_MAX_DIM:
+        raise RuntimeError(f"spd_frechet_mean: 2 <= d <= {_lib.GABO_SPD_MAX_DIM}, got {d}")
+    nb, n = xs.shape[:2]
+    if fused is None:
+        fused = d <= GABO_SPD_MEAN_FUSED_MAX_DIM
+    elif fused and d > GABO_SPD_MEAN_FUSED_MAX_DIM:
+        raise RuntimeError(f"spd_frechet_mean: the fused kernels serve d <= {GABO_SPD_MEAN_FUSED_MAX_DIM}, got {d}")
+    if nb == 0:
+        mean, resid = xs.new_empty(0, xs.shape[-1]), xs.new_empty(0, iters)
+    elif not fused:
+        mean, resid, status = _spd_frechet_mean_composed(xs, w, s, iters, d)
+        _raise_if_not_spd(status, "gabo_spd_frechet_mean", message=_spd_mean_message(nb, n))
+    else:
+        mean = torch.empty(nb, xs.shape[-1], dtype=torch.float64, device=dev)
+        resid = torch.empty(nb, iters, dtype=torch.float64, device=dev) if return_residual else None
+        wsb = lib.gabo_spd_frechet_mean_workspace_bytes(nb, n, d)
+        ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
+        status = _status_word(dev)
+        ptr = lambda t_: None if t_ is None else t_.data_ptr()   # noqa: E731
+        with _on(dev):
+            rc = lib.gabo_spd_frechet_mean(xs.data_ptr(), ptr(w), ptr(s), mean.data_ptr(), ptr(resid), nb, n, d, iters, ws.data_ptr(), wsb,
+                                           status.data_ptr(), _stream_ptr(dev))
+        _lib.check(rc, "gabo_spd_frechet_mean")
+        _raise_if_not_spd(status, "gabo_spd_frechet_mean", message=_spd_mean_message(nb, n))
+    mean = mean.reshape(bshape + (xs.shape[-1],))
+    if return_residual:
+        return _out(mean, out_device), resid.reshape(bshape + (iters,)).to(out_device)
+    return _out(mean, out_device)
+
+
+
+def sphere_karcher_mean(x, weights=None, iters=10, start=None, return_residual=False):
+    """Karcher mean of (N, dim) or (..., N, dim) unit vectors -> (dim,) or (..., dim), on the input's device (the reference's
+    `karcher_mean_sphere`, sphere_utils.py:126-149, for one or many sets; 2 <= dim <= 512).  weights, start, return_residual: as spd_frechet_mean."""
+    lib = _lib.load()
+    first = torch.as_tensor(x)
+    out_device = first.device
+    dev = _device_for(*[torch.as_tensor(t_) for t_ in (x, weights, start) if t_ is not None])
+    iters = int(iters)
+    if iters < 0:
+        raise RuntimeError("iters must be >= 0")
+    xs, w, s, bshape = _mean_args(x, weights, start, "dim", dev)
+    nb, n, dim = xs.shape
+    mean = torch.empty(nb, dim, dtype=torch.float64, device=dev)
+    resid = torch.empty(nb, iters, dtype=torch.float64, device=dev) if return_residual else None
+    if nb > 0:
+        wsb = lib.gabo_sphere_karcher_mean_workspace_bytes(nb, n, dim)
+        ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
+        ptr = lambda t_: None if t_ is None else t_.data_ptr()   # noqa: E731
+        with _on(dev):
+            rc = lib.gabo_sphere_karcher_mean(xs.data_ptr(), ptr(w), ptr(s), mean.data_ptr(), ptr(resid), nb, n, dim, iters, ws.data_ptr(), wsb,
+                                              _stream_ptr(dev))
+        _lib.check(rc, "gabo_sphere_karcher_mean")
+    mean = mean.reshape(bshape + (dim,))
+    if return_residual:
+        return _out(mean, out_device), resid.reshape(bshape + (iters,)).to(out_device)
+    return _out(mean, out_device)

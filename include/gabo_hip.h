@@ -715,6 +715,34 @@ int gabo_sphere_manifold_op(int op, const double* x, const double* u, const doub
                             int dim, gabo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Frechet (Karcher) means: m <- Exp_m(sum_j w_j Log_m(x_j)), `iters` times, the whole chain enqueued without a host wait.
+ * Replaces  mean                    Riemannian_utils/spd_utils.py:235-259      (N x d x d; one non-symmetric numpy eig per point and iteration)
+ *           mean_mandel_vector      Riemannian_utils/spd_utils.py:262-287
+ *           karcher_mean_sphere     Riemannian_utils/sphere_utils.py:126-149
+ * x: batch x n x d_vec Mandel vectors (SPD, affine-invariant metric, 2 <= d <= 10: the fused kernels of csrc/riemannian_mean.hip) or
+ *   batch x n x dim unit vectors (sphere, 2 <= dim <= 512): `batch` independent sets of n points; batch = 1 is the reference's call.
+ * weights: batch x n, non-negative, normalised by their sum inside; NULL = 1/n each (the reference).  A point of weight 0 is skipped: whatever its
+ *   logarithm is (NaN included) stays out of the sum; an SPD data matrix that is not positive definite raises `status` whatever its weight.
+ * start: batch x d_vec (batch x dim); NULL = the set's first point (spd_utils.py:251, sphere_utils.py:143).
+ * mean: batch x d_vec (batch x dim), the result.  iters >= 0 (the reference's default is 10); iters = 0 copies the start point.
+ * residual: NULL, or batch x iters: the norm of the mean tangent sum_j w_j Log_m(x_j) each iteration started from - for SPD its affine-invariant
+ *   norm at m, ||sum_j w_j logm(L^-1 X_j L^-T)||_F with L = chol(m); for the sphere its Euclidean norm.
+ * Per iteration two launches: partial sums over blocks of the data (one wave each, lane = data point), then one wave per set that adds the
+ *   partials in index order and applies Exp_m.  Every sum has a fixed order: the same bits from run to run on one device.
+ * status (SPD): a data matrix, the start point or an iterate that is not positive definite sets {GABO_ERR_NOT_SPD, index}: the index of the
+ *   data matrix (< batch * n), or batch * n + the index of the set whose start point / iterate failed.  A non-positive eigenvalue of
+ *   L^-1 X_j L^-T (rounding of a singular pair) gives NaN, as in gabo_spd_ai_backward.
+ * n < 1, iters < 0, a null x / mean / workspace / status and a workspace smaller than *_workspace_bytes(batch, n, d) return GABO_ERR_ARG,
+ *   d (dim) out of range GABO_ERR_DIM, before any launch.
+ */
+size_t gabo_spd_frechet_mean_workspace_bytes(int64_t batch, int64_t n, int d);
+int gabo_spd_frechet_mean(const double* x, const double* weights, const double* start, double* mean, double* residual, int64_t batch,
+                          int64_t n, int d, int iters, void* workspace, size_t workspace_bytes, int* status, gabo_stream_t stream);
+size_t gabo_sphere_karcher_mean_workspace_bytes(int64_t batch, int64_t n, int dim);
+int gabo_sphere_karcher_mean(const double* x, const double* weights, const double* start, double* mean, double* residual, int64_t batch,
+                             int64_t n, int dim, int iters, void* workspace, size_t workspace_bytes, gabo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Reconstruction cost of the nested-SPD mapping, with its gradient, in one launch (HD-GaBO: the objective of
  * optimize_reconstruction_parameters_nested_spd, nested_mappings/nested_spd_optimization.py:95-186).
  * Replaces  min_affine_invariant_distance_reconstruction_cost   nested_spd_optimization.py:23-56   (metric 0)
