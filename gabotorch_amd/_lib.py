@@ -26,6 +26,7 @@ GABO_METRIC_AFFINE_INVARIANT, GABO_METRIC_LOG_EUCLIDEAN, GABO_METRIC_FROBENIUS =
 GABO_CONSTRAINT_MAX_EIGENVALUE, GABO_CONSTRAINT_MIN_EIGENVALUE = 0, 1
 GABO_CONSTRAINT_MAX_EIGENVALUE_NESTED, GABO_CONSTRAINT_MIN_EIGENVALUE_NESTED = 2, 3
 GABO_SPHERE_CONSTRAINT_COORD_LOWER, GABO_SPHERE_CONSTRAINT_COORD_UPPER, GABO_SPHERE_CONSTRAINT_GEODESIC_BALL = 0, 1, 2
+GABO_SPHERE_SAMPLE_MAX_TRIES = 256
 GABO_TR_SHORTCUT_COUNTERS = 5            # value first, value first then accepted, step reused, fast-forwarded, generic-workspace restarts
 GABO_RECON_AFFINE_INVARIANT, GABO_RECON_LOG_EUCLIDEAN = 0, 1
 GABO_RECON_MAX_LOOKAHEAD = 4
@@ -68,6 +69,12 @@ class SphereSweepConfig(_c.Structure):
     _fields_ = [("acq", SphereAcqParams), ("delta_bar", _c.c_double), ("delta0", _c.c_double), ("theta", _c.c_double), ("kappa", _c.c_double),
                 ("mininner", _c.c_int), ("maxinner", _c.c_int), ("exact_hessian", _c.c_int), ("rho_prime", _c.c_double),
                 ("rho_regularization", _c.c_double), ("mingradnorm", _c.c_double), ("maxiter", _c.c_int64)]
+
+
+class SphereSweepConstraints(_c.Structure):
+    """gabo_sphere_sweep_constraints of include/gabo_hip.h"""
+    _fields_ = [("n_constraints", _c.c_int), ("n_equalities", _c.c_int), ("kind", _c.c_int * 8), ("index", _c.c_int * 8), ("bound", _c.c_double * 8),
+                ("centres", _c.c_void_p), ("n_centres", _c.c_int), ("strict", _c.c_int), ("delta_cons", _c.c_double)]
 
 
 class ReconSolveOptions(_c.Structure):
@@ -132,6 +139,11 @@ SIGNATURES = {
     "gabo_sphere_sweep_score": (_I, [_P, _I64, _I64, _I64, _P, _P, _P, _SZ, _P]),
     "gabo_sphere_sweep_solve": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "gabo_sphere_sweep_run": (_I, [_P, _I64, _I64, _P, _c.c_uint64, _D, _D, _c.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "gabo_sphere_sweep_workspace_bytes_constrained": (_SZ, [_I, _I64, _I64, _I]),
+    "gabo_sphere_sweep_solve_constrained": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "gabo_sphere_sweep_run_constrained": (_I, [_P, _I64, _I64, _P, _c.c_uint64, _D, _D, _c.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ,
+                                               _P]),
+    "gabo_sphere_sample": (_I, [_P, _I64, _I, _c.c_uint64, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
     "gabo_spd_gp_prepare_workspace_bytes": (_SZ, [_I64, _I]),
     "gabo_spd_gp_prepare": (_I, [_P, _P, _I64, _I, _D, _I, _D, _D, _D, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P]),
     "gabo_spd_sweep_rows_workspace_bytes": (_SZ, [_I64, _I, _I64, _I64, _I]),

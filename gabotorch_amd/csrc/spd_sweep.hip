@@ -5,7 +5,7 @@
 // and three behind it).  Round 6: score the raw samples into a table (sampler + evaluation), select the restarts on the device, start every restart
 // from its picked row, solve (ends with the result row) - five launches behind one host wait, plus one host call for the GP's set-up; the tables are laid out so that a multi-GPU
 // sweep all_gathers exactly them.  Below, after the helpers: gabo_spd_gp_prepare, gabo_spd_sweep_score_rows / _select_rows / _solve_rows, then the
-// sphere twin (two host calls around the host heuristic, as in round 5).
+// sphere twin (two host calls around the host heuristic, as in round 5; one call with the selection kernel; both with the library's sphere constraints).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -17,6 +17,7 @@
 #include "spd_tr_body.hpp"
 #include "spd_acq_kernel.hpp"
 #include "gabo_philox.hpp"
+#include "sphere_cons.hpp"
 
 namespace gabo {
 
@@ -418,18 +419,22 @@ extern "C" int gabo_spd_sweep_solve_rows(const gabo_spd_sweep_config* cfg, const
 // ---- the sphere twin: gen_batch_initial_conditions_manifold + gen_candidates_manifold + get_best_candidates on S^(dim-1) ----------------------------
 // The reference's gabo_sphere examples (examples/bo_sphere/benchmark_examples/gabo_sphere.py:151-175): stock TrustRegions, no constraints, exact or
 // finite-difference Hessian-vector products.  Same two-call shape as above; the raw samples always come from the caller's host sampler (`manifold.rand`).
+// The _constrained forms run the same sweep with the library's own sphere constraints (coordinate bounds, great circle, geodesic ball: sphere_cons.hpp)
+// inside the solve launch, and draw the raw samples inside the inequality constraints when the caller hands none over.
 namespace gabo {
 
 struct SphSweepWs {
-    double *raw, *raw_val, *x, *fx, *eg, *g, *ng, *delta;
+    double *raw, *raw_val, *x, *fx, *eg, *g, *ng, *delta, *cons_val;
     int64_t *picked, *picked_rows, *iters;
-    int* flag;
+    int* flag;                  // [0] the selection kernel's fall-back flag, [1] the constrained sampler ran out of tries
     uint8_t* active;
     void* tr;
     size_t tr_bytes, bytes;
 };
 
-static SphSweepWs sph_sweep_layout(void* base, int dim, int64_t max_raw, int64_t r) {
+// c = 0 is the layout of the unconstrained entry points; with c > 0 only the last two blocks (final constraint values, trust-region workspace)
+// differ, so everything the scoring call touches sits at the same offsets in both.
+static SphSweepWs sph_sweep_layout(void* base, int dim, int64_t max_raw, int64_t r, int c = 0) {
     SphSweepWs w;
     char* p = (char*)base;
     auto take = [&](size_t bytes) {
@@ -450,7 +455,8 @@ static SphSweepWs sph_sweep_layout(void* base, int dim, int64_t max_raw, int64_t
     w.iters = (int64_t*)take((size_t)r * 8);
     w.flag = (int*)take(8);
     w.active = (uint8_t*)take((size_t)r);
-    w.tr_bytes = gabo_sphere_tr_workspace_bytes(r, dim, 0);
+    w.cons_val = (double*)take((size_t)r * c * 8);
+    w.tr_bytes = gabo_sphere_tr_workspace_bytes(r, dim, c);
     w.tr = take(w.tr_bytes + 8);
     w.bytes = (size_t)(p - (char*)base);
     return w;
@@ -465,14 +471,10 @@ __global__ __launch_bounds__(256) void sweep_rownorm_kernel(const double* __rest
     out[i] = __builtin_sqrt(s);
 }
 
-// count points uniform on S^(dim-1): normal deviates from the library's Philox stream (seed, sample index), normalised - the distribution of
-// pymanopt's Sphere.rand ([3P]: randn then / norm).  One thread per point.
-__global__ __launch_bounds__(256) void sphere_sample_kernel(double* __restrict__ out, int64_t count, int dim, uint64_t seed) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    Philox ph{(uint32_t)seed, (uint32_t)(seed >> 32), (uint64_t)i, 0u};
+// the point of item `item` of the stream `seed`: normal deviates from the library's Philox stream, normalised
+static __device__ __forceinline__ void sphere_sample_row(double* row, int dim, uint64_t seed, uint64_t item) {
+    Philox ph{(uint32_t)seed, (uint32_t)(seed >> 32), item, 0u};
     ph.tag = 0x73706872u;      // "sphr": this sampler's stream
-    double* row = out + i * dim;
     double ss = 0.0;
     for (int k = 0; k < dim; k += 2) {
         double z0, z1;
@@ -488,6 +490,31 @@ __global__ __launch_bounds__(256) void sphere_sample_kernel(double* __restrict__
     for (int k = 0; k < dim; ++k) row[k] *= inv;
 }
 
+// count points uniform on S^(dim-1): normal deviates from the library's Philox stream (seed, sample index), normalised - the distribution of
+// pymanopt's Sphere.rand ([3P]: randn then / norm).  One thread per point.
+__global__ __launch_bounds__(256) void sphere_sample_kernel(double* __restrict__ out, int64_t count, int dim, uint64_t seed) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    sphere_sample_row(out + i * dim, dim, seed, (uint64_t)i);
+}
+
+// The same points inside the library's inequality constraints, by rejection - what the reference's constrained examples do on the host when they replace
+// `manifold.rand` by a sampler of feasible points.  One thread per point: try t of sample i is item i + t * count of the stream above, accepted when every
+// constraint is strictly positive there (a NaN rejects), so with no constraint the output is sphere_sample_kernel's and the whole draw is rows of ONE
+// unconstrained stream of count * tries items.  A sample still infeasible after GABO_SPHERE_SAMPLE_MAX_TRIES keeps its last try and raises *exhausted.
+__global__ __launch_bounds__(256) void sphere_sample_constrained_kernel(double* __restrict__ out, int64_t count, int dim, uint64_t seed, SphCons K,
+                                                                        int* __restrict__ exhausted) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    double* row = out + i * dim;
+    bool ok = false;
+    for (int t = 0; t < GABO_SPHERE_SAMPLE_MAX_TRIES && !ok; ++t) {
+        sphere_sample_row(row, dim, seed, (uint64_t)i + (uint64_t)t * (uint64_t)count);
+        ok = sph_cons_all_positive(row, dim, K);
+    }
+    if (!ok) atomicOr(exhausted, 1);
+}
+
 // dst row i = src row idx[i], the index clamped into the table (when the selection kernel raised its fall-back flag it picked nothing: the launches behind
 // it then work on whatever rows these are, and the caller discards the result)
 __global__ __launch_bounds__(256) void sweep_gather_clamped_kernel(const double* __restrict__ src, const int64_t* __restrict__ idx, double* __restrict__ dst,
@@ -499,11 +526,159 @@ __global__ __launch_bounds__(256) void sweep_gather_clamped_kernel(const double*
     dst[e] = src[k * dim + e % dim];
 }
 
+// the constraint set of a sweep checked as gabo_sphere_tr_solve_constrained checks it, before any HIP call (NULL: no constraints)
+static int sph_sweep_cons_ok(const gabo_sphere_sweep_constraints* cons, int dim, SphCons* K) {
+    if (!cons) return sph_cons_ok(0, 0, nullptr, nullptr, nullptr, nullptr, 0, dim, 0, 0.0, K);
+    if (cons->n_constraints < 0 || cons->n_constraints > kMaxCons) return GABO_ERR_ARG;      // (before the fixed-size arrays are read)
+    return sph_cons_ok(cons->n_constraints, cons->n_equalities, cons->kind, cons->index, cons->bound, cons->centres, cons->n_centres, dim, cons->strict,
+                       cons->delta_cons, K);
+}
+
+struct SphSweepOut {
+    int64_t *best_index_host, *max_iterations_host;
+    double* best_value_host;
+    double **candidates_dev, **cost_dev, **constraint_values_dev;
+    int64_t **iterations_dev, **picked_dev;
+};
+
+// The shared tail of the sweep's entry points, behind the indices of the restarts' raw samples in w.picked: gather (clamped into `clamp_rows` rows when
+// a kernel picked them), evaluate, project, norm, init, solve (the constrained launch only when there are constraints), final constraint values,
+// read-back with ONE wait, arg-max.  flags_host (n_flags ints, may be 0): w.flag as the launches left it; when one of them is raised nothing is reported.
+static int sph_sweep_tail(const gabo_sphere_sweep_config* cfg, const gabo_sphere_sweep_constraints* cons, const SphSweepWs& w, int64_t r,
+                          int64_t clamp_rows, int* flags_host, int n_flags, const SphSweepOut& out, gabo_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int dim = cfg->acq.dim;
+    const int c = cons ? cons->n_constraints : 0;
+    int rc;
+    if (clamp_rows > 0)
+        hipLaunchKernelGGL(sweep_gather_clamped_kernel, dim3((unsigned)((r * dim + 255) / 256)), dim3(256), 0, st, w.raw, w.picked, w.x, r, dim, clamp_rows);
+    else
+        hipLaunchKernelGGL(sweep_gather_kernel, dim3((unsigned)((r * dim + 255) / 256)), dim3(256), 0, st, w.raw, w.picked, w.x, r, dim);
+    gabo_sphere_acq_params acq = cfg->acq;
+    acq.out_sign = -1.0;
+    if ((rc = gabo_sphere_acq_eval(w.x, &acq, w.fx, w.eg, r, stream)) != GABO_OK) return rc;
+    if ((rc = gabo_sphere_manifold_op(GABO_SPH_PROJ, w.x, w.eg, nullptr, nullptr, w.g, r, dim, stream)) != GABO_OK) return rc;
+    hipLaunchKernelGGL(sweep_rownorm_kernel, dim3((unsigned)((r + 255) / 256)), dim3(256), 0, st, w.g, w.ng, r, dim);
+    hipLaunchKernelGGL(sweep_init_kernel, dim3((unsigned)((r + 255) / 256)), dim3(256), 0, st, w.delta, w.active, w.iters, r, cfg->delta0);
+    if (hipMemsetAsync(w.tr, 0, w.tr_bytes, st) != hipSuccess) return GABO_ERR_LAUNCH;
+    if (c == 0) {
+        rc = gabo_sphere_tr_solve(w.x, w.fx, w.g, w.ng, w.delta, w.active, w.iters, &acq, w.tr, w.tr_bytes, r, cfg->theta, cfg->kappa, cfg->mininner,
+                                  cfg->maxinner, cfg->exact_hessian, cfg->delta_bar, cfg->rho_prime, cfg->rho_regularization, cfg->mingradnorm,
+                                  cfg->maxiter, stream);
+    } else {
+        rc = gabo_sphere_tr_solve_constrained(w.x, w.fx, w.g, w.ng, w.delta, w.active, w.iters, &acq, w.tr, w.tr_bytes, r, cfg->theta, cfg->kappa,
+                                              cfg->mininner, cfg->maxinner, cfg->exact_hessian, cfg->delta_bar, cfg->rho_prime, cfg->rho_regularization,
+                                              cfg->mingradnorm, cfg->maxiter, c, cons->n_equalities, cons->kind, cons->index, cons->bound, cons->centres,
+                                              cons->n_centres, cons->strict, cons->delta_cons, stream);
+        if (rc == GABO_OK)      // the constraints at the final iterates, values only
+            rc = gabo_sphere_constraints_eval(w.x, r, dim, c, cons->kind, cons->index, cons->bound, cons->centres, cons->n_centres, w.cons_val, nullptr,
+                                              stream);
+    }
+    if (rc != GABO_OK) return rc;
+    std::vector<double> fx((size_t)r);
+    std::vector<int64_t> it((size_t)r);
+    if (hipMemcpyAsync(fx.data(), w.fx, (size_t)r * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return GABO_ERR_LAUNCH;
+    if (hipMemcpyAsync(it.data(), w.iters, (size_t)r * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return GABO_ERR_LAUNCH;
+    if (n_flags > 0 && hipMemcpyAsync(flags_host, w.flag, (size_t)n_flags * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return GABO_ERR_LAUNCH;
+    if (hipStreamSynchronize(st) != hipSuccess) return GABO_ERR_LAUNCH;
+    for (int k = 0; k < n_flags; ++k)
+        if (flags_host[k] != 0) return GABO_OK;
+    int64_t best = 0, maxit = 0;
+    for (int64_t k = 0; k < r; ++k) {
+        const double v = -fx[(size_t)k], b = -fx[(size_t)best];
+        if ((v > b && b == b) || (v != v && b == b)) best = k;
+        if (it[(size_t)k] > maxit) maxit = it[(size_t)k];
+    }
+    *out.best_index_host = best;
+    *out.best_value_host = -fx[(size_t)best];
+    if (out.max_iterations_host) *out.max_iterations_host = maxit;
+    if (out.candidates_dev) *out.candidates_dev = w.x;
+    if (out.cost_dev) *out.cost_dev = w.fx;
+    if (out.iterations_dev) *out.iterations_dev = w.iters;
+    if (out.picked_dev) *out.picked_dev = w.picked;          // the raw-sample index of every restart
+    if (out.constraint_values_dev) *out.constraint_values_dev = c > 0 ? w.cons_val : nullptr;
+    return GABO_OK;
+}
+
+// gabo_sphere_sweep_solve[_constrained]: the caller's picks to the device, then the tail
+static int sph_sweep_solve(const gabo_sphere_sweep_config* cfg, const gabo_sphere_sweep_constraints* cons, const int64_t* picked_host, int64_t restarts,
+                           int64_t max_raw, const SphSweepOut& out, void* workspace, size_t workspace_bytes, gabo_stream_t stream) {
+    if (!cfg || !picked_host || !out.best_index_host || !out.best_value_host || !workspace || restarts < 1) return GABO_ERR_ARG;
+    const int dim = cfg->acq.dim;
+    if (dim < 2) return GABO_ERR_DIM;
+    SphCons K;
+    int rc = sph_sweep_cons_ok(cons, dim, &K);
+    if (rc != GABO_OK) return rc;
+    const int64_t r = restarts;
+    for (int64_t k = 0; k < r; ++k)
+        if (picked_host[k] < 0 || picked_host[k] >= max_raw) return GABO_ERR_ARG;
+    const SphSweepWs w = sph_sweep_layout(workspace, dim, max_raw, r, K.n);
+    if (w.bytes > workspace_bytes) return GABO_ERR_ARG;
+    if (hipMemcpyAsync(w.picked, picked_host, (size_t)r * 8, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) return GABO_ERR_LAUNCH;
+    return sph_sweep_tail(cfg, K.n ? cons : nullptr, w, r, 0, nullptr, 0, out, stream);
+}
+
+// gabo_sphere_sweep_run[_constrained]: raw samples (the caller's, or drawn here) -> values -> selection kernel -> the tail
+static int sph_sweep_run(const gabo_sphere_sweep_config* cfg, const gabo_sphere_sweep_constraints* cons, int64_t count, int64_t restarts,
+                         const double* raw_points_host, uint64_t sample_seed, double eta, double alpha, uint64_t select_seed, int* fallback_host,
+                         const SphSweepOut& out, void* workspace, size_t workspace_bytes, gabo_stream_t stream) {
+    if (!cfg || !out.best_index_host || !out.best_value_host || !fallback_host || !workspace || count < 1 || restarts < 1) return GABO_ERR_ARG;
+    if (!gabo_spd_sweep_select_supported(count, restarts)) return GABO_ERR_DIM;
+    const int dim = cfg->acq.dim;
+    if (dim < 2) return GABO_ERR_DIM;
+    SphCons K;
+    int rc = sph_sweep_cons_ok(cons, dim, &K);
+    if (rc != GABO_OK) return rc;
+    if (!raw_points_host && K.neq > 0) return GABO_ERR_ARG;      // (no device sampler ON an equality constraint: the caller's host sampler draws there)
+    const int64_t r = restarts;
+    const SphSweepWs w = sph_sweep_layout(workspace, dim, count, r, K.n);
+    if (w.bytes > workspace_bytes) return GABO_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const bool sampler = !raw_points_host && K.n > 0;
+    if (raw_points_host) {
+        if (hipMemcpyAsync(w.raw, raw_points_host, (size_t)count * dim * 8, hipMemcpyHostToDevice, st) != hipSuccess) return GABO_ERR_LAUNCH;
+    } else if (sampler) {
+        if (hipMemsetAsync(w.flag, 0, 2 * sizeof(int), st) != hipSuccess) return GABO_ERR_LAUNCH;
+        hipLaunchKernelGGL(sphere_sample_constrained_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, w.raw, count, dim, sample_seed, K,
+                           w.flag + 1);
+    } else {
+        hipLaunchKernelGGL(sphere_sample_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, w.raw, count, dim, sample_seed);
+    }
+    gabo_sphere_acq_params acq = cfg->acq;
+    acq.out_sign = 1.0;
+    if ((rc = gabo_sphere_acq_eval(w.raw, &acq, w.raw_val, nullptr, count, stream)) != GABO_OK) return rc;
+    {   // selection: the values as a one-column table whose row 1 + k is sample k (sweep_select_kernel's addressing with one block of `count` rows)
+        size_t p2 = 1;
+        while ((int64_t)p2 < count) p2 <<= 1;
+        const size_t lds = p2 * 12 + 1024 * 12;
+        static std::atomic<uint64_t> attr_set{0};
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return GABO_ERR_LAUNCH;
+        if (!(attr_set.load(std::memory_order_acquire) >> dev & 1)) {
+            if (hipFuncSetAttribute((const void*)sweep_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(kSelectMaxTotal * 12 + 1024 * 12)) != hipSuccess)
+                return GABO_ERR_LAUNCH;
+            attr_set.fetch_or((uint64_t)1 << dev, std::memory_order_release);
+        }
+        hipLaunchKernelGGL(sweep_select_kernel, dim3(1), dim3(1024), lds, st, w.raw_val - 1, (int64_t)1, (int)count, (int)count, (int)r, eta, alpha,
+                           select_seed, 0, 0, 1, w.picked_rows, w.picked, w.flag, (int*)nullptr);
+    }
+    int flags[2] = {0, 0};
+    if ((rc = sph_sweep_tail(cfg, K.n ? cons : nullptr, w, r, count, flags, sampler ? 2 : 1, out, stream)) != GABO_OK) return rc;
+    *fallback_host = flags[1] != 0 ? 2 : (flags[0] != 0 ? 1 : 0);
+    return GABO_OK;
+}
+
 }  // namespace gabo
 
 extern "C" size_t gabo_sphere_sweep_workspace_bytes(int dim, int64_t max_raw, int64_t restarts) {
     if (dim < 2 || max_raw < 0 || restarts < 0) return 0;
     return gabo::sph_sweep_layout(nullptr, dim, max_raw, restarts).bytes;
+}
+
+extern "C" size_t gabo_sphere_sweep_workspace_bytes_constrained(int dim, int64_t max_raw, int64_t restarts, int n_constraints) {
+    if (dim < 2 || max_raw < 0 || restarts < 0 || n_constraints < 0 || n_constraints > gabo::kMaxCons) return 0;
+    return gabo::sph_sweep_layout(nullptr, dim, max_raw, restarts, n_constraints).bytes;
 }
 
 extern "C" int gabo_sphere_sweep_score(const gabo_sphere_sweep_config* cfg, int64_t count, int64_t max_raw, int64_t restarts,
@@ -529,47 +704,19 @@ extern "C" int gabo_sphere_sweep_solve(const gabo_sphere_sweep_config* cfg, cons
                                        int64_t* best_index_host, double* best_value_host, int64_t* max_iterations_host, double** candidates_dev,
                                        double** cost_dev, int64_t** iterations_dev, void* workspace, size_t workspace_bytes,
                                        gabo_stream_t stream) {
-    if (!cfg || !picked_host || !best_index_host || !best_value_host || !workspace || restarts < 1) return GABO_ERR_ARG;
-    const int dim = cfg->acq.dim;
-    if (dim < 2) return GABO_ERR_DIM;
-    const int64_t r = restarts;
-    for (int64_t k = 0; k < r; ++k)
-        if (picked_host[k] < 0 || picked_host[k] >= max_raw) return GABO_ERR_ARG;
-    const gabo::SphSweepWs w = gabo::sph_sweep_layout(workspace, dim, max_raw, r);
-    if (w.bytes > workspace_bytes) return GABO_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (hipMemcpyAsync(w.picked, picked_host, (size_t)r * 8, hipMemcpyHostToDevice, st) != hipSuccess) return GABO_ERR_LAUNCH;
-    hipLaunchKernelGGL(gabo::sweep_gather_kernel, dim3((unsigned)((r * dim + 255) / 256)), dim3(256), 0, st, w.raw, w.picked, w.x, r, dim);
-    gabo_sphere_acq_params acq = cfg->acq;
-    acq.out_sign = -1.0;
-    if ((rc = gabo_sphere_acq_eval(w.x, &acq, w.fx, w.eg, r, stream)) != GABO_OK) return rc;
-    if ((rc = gabo_sphere_manifold_op(GABO_SPH_PROJ, w.x, w.eg, nullptr, nullptr, w.g, r, dim, stream)) != GABO_OK) return rc;
-    hipLaunchKernelGGL(gabo::sweep_rownorm_kernel, dim3((unsigned)((r + 255) / 256)), dim3(256), 0, st, w.g, w.ng, r, dim);
-    hipLaunchKernelGGL(gabo::sweep_init_kernel, dim3((unsigned)((r + 255) / 256)), dim3(256), 0, st, w.delta, w.active, w.iters, r, cfg->delta0);
-    if (hipMemsetAsync(w.tr, 0, w.tr_bytes, st) != hipSuccess) return GABO_ERR_LAUNCH;
-    if ((rc = gabo_sphere_tr_solve(w.x, w.fx, w.g, w.ng, w.delta, w.active, w.iters, &acq, w.tr, w.tr_bytes, r, cfg->theta, cfg->kappa, cfg->mininner,
-                                   cfg->maxinner, cfg->exact_hessian, cfg->delta_bar, cfg->rho_prime, cfg->rho_regularization, cfg->mingradnorm,
-                                   cfg->maxiter, stream)) != GABO_OK)
-        return rc;
-    std::vector<double> fx((size_t)r);
-    std::vector<int64_t> it((size_t)r);
-    if (hipMemcpyAsync(fx.data(), w.fx, (size_t)r * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return GABO_ERR_LAUNCH;
-    if (hipMemcpyAsync(it.data(), w.iters, (size_t)r * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return GABO_ERR_LAUNCH;
-    if (hipStreamSynchronize(st) != hipSuccess) return GABO_ERR_LAUNCH;
-    int64_t best = 0, maxit = 0;
-    for (int64_t k = 0; k < r; ++k) {
-        const double v = -fx[(size_t)k], b = -fx[(size_t)best];
-        if ((v > b && b == b) || (v != v && b == b)) best = k;
-        if (it[(size_t)k] > maxit) maxit = it[(size_t)k];
-    }
-    *best_index_host = best;
-    *best_value_host = -fx[(size_t)best];
-    if (max_iterations_host) *max_iterations_host = maxit;
-    if (candidates_dev) *candidates_dev = w.x;
-    if (cost_dev) *cost_dev = w.fx;
-    if (iterations_dev) *iterations_dev = w.iters;
-    return GABO_OK;
+    const gabo::SphSweepOut out{best_index_host, max_iterations_host, best_value_host, candidates_dev, cost_dev, nullptr, iterations_dev, nullptr};
+    return gabo::sph_sweep_solve(cfg, nullptr, picked_host, restarts, max_raw, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gabo_sphere_sweep_solve_constrained(const gabo_sphere_sweep_config* cfg, const int64_t* picked_host, int64_t restarts, int64_t max_raw,
+                                                   int64_t* best_index_host, double* best_value_host, int64_t* max_iterations_host,
+                                                   double** candidates_dev, double** cost_dev, int64_t** iterations_dev,
+                                                   const gabo_sphere_sweep_constraints* constraints, double** constraint_values_dev, void* workspace,
+                                                   size_t workspace_bytes, gabo_stream_t stream) {
+    if (!constraints) return GABO_ERR_ARG;
+    const gabo::SphSweepOut out{best_index_host, max_iterations_host, best_value_host, candidates_dev, cost_dev, constraint_values_dev, iterations_dev,
+                                nullptr};
+    return gabo::sph_sweep_solve(cfg, constraints, picked_host, restarts, max_raw, out, workspace, workspace_bytes, stream);
 }
 
 // The same sweep in ONE host call with one wait: raw samples (the caller's, or drawn here on the library's Philox stream when raw_points_host is null) ->
@@ -581,71 +728,39 @@ extern "C" int gabo_sphere_sweep_run(const gabo_sphere_sweep_config* cfg, int64_
                                      int64_t* max_iterations_host, double** candidates_dev, double** cost_dev, int64_t** iterations_dev, int64_t** picked_dev,
                                      int* fallback_host,
                                      void* workspace, size_t workspace_bytes, gabo_stream_t stream) {
-    if (!cfg || !best_index_host || !best_value_host || !fallback_host || !workspace || count < 1 || restarts < 1) return GABO_ERR_ARG;
-    if (!gabo_spd_sweep_select_supported(count, restarts)) return GABO_ERR_DIM;
-    const int dim = cfg->acq.dim;
-    if (dim < 2) return GABO_ERR_DIM;
-    const int64_t r = restarts;
-    const gabo::SphSweepWs w = gabo::sph_sweep_layout(workspace, dim, count, r);
-    if (w.bytes > workspace_bytes) return GABO_ERR_ARG;
+    const gabo::SphSweepOut out{best_index_host, max_iterations_host, best_value_host, candidates_dev, cost_dev, nullptr, iterations_dev, picked_dev};
+    return gabo::sph_sweep_run(cfg, nullptr, count, restarts, raw_points_host, sample_seed, eta, alpha, select_seed, fallback_host, out, workspace,
+                               workspace_bytes, stream);
+}
+
+// ... with the library's sphere constraints inside the solve; raw_points_host null draws inside the inequality constraints (sphere_sample_constrained_kernel).
+// *fallback_host = 2: that sampler ran out of tries for some sample; nothing else is valid and the caller samples on the host.
+extern "C" int gabo_sphere_sweep_run_constrained(const gabo_sphere_sweep_config* cfg, int64_t count, int64_t restarts, const double* raw_points_host,
+                                                 uint64_t sample_seed, double eta, double alpha, uint64_t select_seed, int64_t* best_index_host,
+                                                 double* best_value_host, int64_t* max_iterations_host, double** candidates_dev, double** cost_dev,
+                                                 int64_t** iterations_dev, int64_t** picked_dev, int* fallback_host,
+                                                 const gabo_sphere_sweep_constraints* constraints, double** constraint_values_dev, void* workspace,
+                                                 size_t workspace_bytes, gabo_stream_t stream) {
+    if (!constraints) return GABO_ERR_ARG;
+    const gabo::SphSweepOut out{best_index_host, max_iterations_host, best_value_host, candidates_dev, cost_dev, constraint_values_dev, iterations_dev,
+                                picked_dev};
+    return gabo::sph_sweep_run(cfg, constraints, count, restarts, raw_points_host, sample_seed, eta, alpha, select_seed, fallback_host, out, workspace,
+                               workspace_bytes, stream);
+}
+
+// The sampler alone: count points of S^(dim-1) inside the inequality constraints into `out` (count x dim, device), *exhausted_dev (device) set to 0 or 1.
+extern "C" int gabo_sphere_sample(double* out, int64_t count, int dim, uint64_t seed, int n_constraints, int n_equalities, const int* kind, const int* index,
+                                  const double* bound, const double* centres, int n_centres, int* exhausted_dev, gabo_stream_t stream) {
+    if (dim < 2 || dim > 512) return GABO_ERR_DIM;
+    gabo::SphCons K;
+    int rc = gabo::sph_cons_ok(n_constraints, n_equalities, kind, index, bound, centres, n_centres, dim, 0, 0.0, &K);
+    if (rc != GABO_OK) return rc;
+    if (n_equalities > 0 || count < 0 || count > 0x7fffffffLL) return GABO_ERR_ARG;
+    if (count == 0) return GABO_OK;
+    if (!out || !exhausted_dev) return GABO_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (raw_points_host) {
-        if (hipMemcpyAsync(w.raw, raw_points_host, (size_t)count * dim * 8, hipMemcpyHostToDevice, st) != hipSuccess) return GABO_ERR_LAUNCH;
-    } else {
-        hipLaunchKernelGGL(gabo::sphere_sample_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, w.raw, count, dim, sample_seed);
-    }
-    gabo_sphere_acq_params acq = cfg->acq;
-    acq.out_sign = 1.0;
-    if ((rc = gabo_sphere_acq_eval(w.raw, &acq, w.raw_val, nullptr, count, stream)) != GABO_OK) return rc;
-    {   // selection: the values as a one-column table whose row 1 + k is sample k (sweep_select_kernel's addressing with one block of `count` rows)
-        size_t p2 = 1;
-        while ((int64_t)p2 < count) p2 <<= 1;
-        const size_t lds = p2 * 12 + 1024 * 12;
-        static std::atomic<uint64_t> attr_set{0};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return GABO_ERR_LAUNCH;
-        if (!(attr_set.load(std::memory_order_acquire) >> dev & 1)) {
-            if (hipFuncSetAttribute((const void*)gabo::sweep_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(gabo::kSelectMaxTotal * 12 + 1024 * 12)) != hipSuccess)
-                return GABO_ERR_LAUNCH;
-            attr_set.fetch_or((uint64_t)1 << dev, std::memory_order_release);
-        }
-        hipLaunchKernelGGL(gabo::sweep_select_kernel, dim3(1), dim3(1024), lds, st, w.raw_val - 1, (int64_t)1, (int)count, (int)count, (int)r, eta, alpha,
-                           select_seed, 0, 0, 1, w.picked_rows, w.picked, w.flag, (int*)nullptr);
-    }
-    hipLaunchKernelGGL(gabo::sweep_gather_clamped_kernel, dim3((unsigned)((r * dim + 255) / 256)), dim3(256), 0, st, w.raw, w.picked, w.x, r, dim, count);
-    acq.out_sign = -1.0;
-    if ((rc = gabo_sphere_acq_eval(w.x, &acq, w.fx, w.eg, r, stream)) != GABO_OK) return rc;
-    if ((rc = gabo_sphere_manifold_op(GABO_SPH_PROJ, w.x, w.eg, nullptr, nullptr, w.g, r, dim, stream)) != GABO_OK) return rc;
-    hipLaunchKernelGGL(gabo::sweep_rownorm_kernel, dim3((unsigned)((r + 255) / 256)), dim3(256), 0, st, w.g, w.ng, r, dim);
-    hipLaunchKernelGGL(gabo::sweep_init_kernel, dim3((unsigned)((r + 255) / 256)), dim3(256), 0, st, w.delta, w.active, w.iters, r, cfg->delta0);
-    if (hipMemsetAsync(w.tr, 0, w.tr_bytes, st) != hipSuccess) return GABO_ERR_LAUNCH;
-    if ((rc = gabo_sphere_tr_solve(w.x, w.fx, w.g, w.ng, w.delta, w.active, w.iters, &acq, w.tr, w.tr_bytes, r, cfg->theta, cfg->kappa, cfg->mininner,
-                                   cfg->maxinner, cfg->exact_hessian, cfg->delta_bar, cfg->rho_prime, cfg->rho_regularization, cfg->mingradnorm,
-                                   cfg->maxiter, stream)) != GABO_OK)
-        return rc;
-    std::vector<double> fx((size_t)r);
-    std::vector<int64_t> it((size_t)r);
-    int flag = 0;
-    if (hipMemcpyAsync(fx.data(), w.fx, (size_t)r * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return GABO_ERR_LAUNCH;
-    if (hipMemcpyAsync(it.data(), w.iters, (size_t)r * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return GABO_ERR_LAUNCH;
-    if (hipMemcpyAsync(&flag, w.flag, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return GABO_ERR_LAUNCH;
-    if (hipStreamSynchronize(st) != hipSuccess) return GABO_ERR_LAUNCH;
-    *fallback_host = flag != 0 ? 1 : 0;
-    if (flag != 0) return GABO_OK;
-    int64_t best = 0, maxit = 0;
-    for (int64_t k = 0; k < r; ++k) {
-        const double v = -fx[(size_t)k], b = -fx[(size_t)best];
-        if ((v > b && b == b) || (v != v && b == b)) best = k;
-        if (it[(size_t)k] > maxit) maxit = it[(size_t)k];
-    }
-    *best_index_host = best;
-    *best_value_host = -fx[(size_t)best];
-    if (max_iterations_host) *max_iterations_host = maxit;
-    if (candidates_dev) *candidates_dev = w.x;
-    if (cost_dev) *cost_dev = w.fx;
-    if (iterations_dev) *iterations_dev = w.iters;
-    if (picked_dev) *picked_dev = w.picked;          // the raw-sample index of every restart
-    return GABO_OK;
+    if (hipMemsetAsync(exhausted_dev, 0, sizeof(int), st) != hipSuccess) return GABO_ERR_LAUNCH;
+    hipLaunchKernelGGL(gabo::sphere_sample_constrained_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, out, count, dim, seed, K,
+                       exhausted_dev);
+    return hipGetLastError() == hipSuccess ? GABO_OK : GABO_ERR_LAUNCH;
 }

@@ -12,6 +12,7 @@
 //   gabo_sphere_constraints_eval   values and Riemannian gradients of those constraints at R points, one launch
 // The scalar logic of the tCG iteration is tcg_step_core of spd_tcg_body.hpp (shared with the SPD kernels).
 #include "spd_tcg_body.hpp"
+#include "sphere_cons.hpp"
 
 namespace gabo {
 
@@ -469,29 +470,13 @@ static __device__ __forceinline__ bool sph_update_body(double* __restrict__ x, d
     return !(ngi < mingradnorm || it >= maxiter);
 }
 
-// The library's own sphere constraints (Riemannian_utils/sphere_constraints_utils_torch.py; kinds GABO_SPHERE_CONSTRAINT_*), equalities first.
-// A kernel argument: kind / index / bound are read with wave-uniform indices.
-struct SphCons {
-    int n, neq, strict;
-    int kind[kMaxCons];
-    int index[kMaxCons];        // the coordinate, or the row of `centres` for the ball
-    double bound[kMaxCons];
-    double delta_cons;
-    const double* centres;      // n_centres x dim
+// The library's own sphere constraints (SphCons and the statement of every kind: sphere_cons.hpp), here with the wave's inner product:
+// value of constraint k at x (dim doubles, global or LDS); the same in every lane.  *inner: <x, centre> of a ball.
+struct SphWaveDot {
+    __device__ __forceinline__ double operator()(const double* a, const double* b, int n) const { return dotg(a, b, n); }
 };
-
-// value of constraint k at x (dim doubles, global or LDS), written as the torch function states it; the same in every lane.
-// *inner: <x, centre> of a ball.
 static __device__ __forceinline__ double sph_cons_value(const double* __restrict__ x, int dim, const SphCons& K, int k, double* inner) {
-    const int kind = K.kind[k], j = K.index[k];
-    const double b = K.bound[k];
-    if (kind == GABO_SPHERE_CONSTRAINT_GEODESIC_BALL) {
-        const double c = dotg(x, K.centres + (int64_t)j * dim, dim);
-        *inner = c;
-        const double cc = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
-        return b - acos(cc);
-    }
-    return kind == GABO_SPHERE_CONSTRAINT_COORD_LOWER ? x[j] - b : b - x[j];
+    return sph_cons_value(x, dim, K, k, inner, SphWaveDot{});
 }
 
 // values fc[k] and (gc != nullptr) Riemannian gradients proj_x(egrad) gc[k * gc_stride + e] of the K.n constraints at x.  The ball's gradient is
@@ -675,28 +660,6 @@ static int sph_acq_ok(const SphAcq* a) {
     if (a->kind != GABO_ACQ_EXPECTED_IMPROVEMENT && a->kind != GABO_ACQ_POSTERIOR_MEAN) return GABO_ERR_ARG;
     if (a->kind == GABO_ACQ_EXPECTED_IMPROVEMENT && (!a->linv || !a->linv_t)) return GABO_ERR_ARG;
     if ((size_t)(7 * a->n + 6 * a->dim) * sizeof(double) > 150 * 1024) return GABO_ERR_ARG;
-    return GABO_OK;
-}
-
-// the host arrays of a constraint set checked and packed into the kernel argument
-static int sph_cons_ok(int n, int neq, const int* kind, const int* index, const double* bound, const double* centres, int n_centres, int dim,
-                       int strict, double delta_cons, SphCons* K) {
-    if (n < 0 || n > kMaxCons || neq < 0 || neq > n || n_centres < 0) return GABO_ERR_ARG;
-    if (n > 0 && (!kind || !index || !bound)) return GABO_ERR_ARG;
-    *K = SphCons{};
-    K->n = n;
-    K->neq = neq;
-    K->strict = strict != 0;
-    K->delta_cons = delta_cons;
-    K->centres = centres;
-    for (int k = 0; k < n; ++k) {
-        const bool coord = kind[k] == GABO_SPHERE_CONSTRAINT_COORD_LOWER || kind[k] == GABO_SPHERE_CONSTRAINT_COORD_UPPER;
-        if (!coord && kind[k] != GABO_SPHERE_CONSTRAINT_GEODESIC_BALL) return GABO_ERR_ARG;
-        if (index[k] < 0 || index[k] >= (coord ? dim : n_centres) || (!coord && !centres)) return GABO_ERR_ARG;
-        K->kind[k] = kind[k];
-        K->index[k] = index[k];
-        K->bound[k] = bound[k];
-    }
     return GABO_OK;
 }
 

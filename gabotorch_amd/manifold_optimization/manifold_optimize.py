@@ -425,19 +425,29 @@ def _native_sweep_plan(acq_function, manifold, solver, q, num_restarts, raw_samp
     if isinstance(manifold, Sphere):
         if _dist() is not None:
             return None       # (the sphere twin has no sharded form: the Python path below shards it)
-        # the sphere twin (gabo_sphere_sweep_score / _solve): stock trust regions without constraints, exact or FD Hessian, host sampler
+        # the sphere twin (gabo_sphere_sweep_score / _solve / _run and their _constrained forms): the package's trust regions, exact or FD Hessian,
+        # no constraints or the library's own sphere constraints (coordinate bounds, great circle, geodesic ball built with functools.partial: what
+        # the solve launch evaluates itself); any other constraint is a host callable and keeps the Python path
         if not (q == 1 and bounds is None and not solver_init_conds and sample_type == torch.float64 and isinstance(solver, BatchedTrustRegions)
-                and not solver.use_rand and solver.maxtime >= 1000 and solver.trace is None and not equality_constraints
-                and not inequality_constraints and pre_processing_manifold is None and post_processing_manifold is None):
+                and not solver.use_rand and solver.maxtime >= 1000 and solver.trace is None
+                and pre_processing_manifold is None and post_processing_manifold is None):
             return None
         dev = torch.device(device)
         if dev.type != "cuda":
             return None
+        as_list = lambda c: list(c) if isinstance(c, (list, tuple)) else ([c] if c else [])       # noqa: E731  (BatchedTrustRegions._solve's reading)
+        eqs, ineqs = as_list(equality_constraints), as_list(inequality_constraints)
+        group = None
+        if eqs or ineqs:
+            from ..Riemannian_utils.sphere_constraints_utils_torch import builtin_sphere_group
+            group = builtin_sphere_group(eqs + ineqs, int(manifold._n), dev)
+            if group is None:
+                return None
         fused = FusedAcquisition.build(acq_function, None, dev)
         if fused is None or not (fused.family == "sphere" and fused.single_launch):
             return None
         return {"fused": fused, "device": dev, "manifold": manifold, "builtins": [], "device_rand": False, "sphere": True,
-                "exact_hessian": not approx_hessian}
+                "exact_hessian": not approx_hessian, "sphere_group": group, "n_equalities": len(eqs)}
     if not (q == 1 and bounds is None and not solver_init_conds and approx_hessian and sample_type == torch.float64
             and isinstance(solver, BatchedTrustRegions) and not solver.use_rand and solver.maxtime >= 1000
             and solver.trace is None and not equality_constraints):
@@ -703,7 +713,27 @@ def _native_sweep(plan, acq_function, solver, num_restarts, raw_samples, options
 
 
 def _native_sweep_sphere(plan, acq_function, solver, num_restarts, raw_samples, options):
-    """the sphere twin of _native_sweep: gabo_sphere_sweep_score / gabo_sphere_sweep_solve around the same selection heuristic and host sampler"""
+    """The sphere twin of _native_sweep (csrc/spd_sweep.hip), without constraints or with the library's own sphere constraints (plan["sphere_group"]:
+    the _constrained entry points, the constraints evaluated inside the solve launch).  Two forms:
+
+      * two calls - gabo_sphere_sweep_score, select_rows on the host with torch's generator, gabo_sphere_sweep_solve[_constrained].  numpy's and
+        torch's generators are consumed exactly as on the Python path and the device executes its statements, so a seeded sweep returns the Python
+        path's candidate, costs and iteration counts bit for bit.  The default WITH constraints (options["device_selection"] defaults to False there:
+        seeded constrained sweeps keep the candidates they returned when the sweep around the solve was Python), and what runs whenever the one-call
+        form does not apply or falls back;
+      * one call, one host wait - gabo_sphere_sweep_run[_constrained]: the selection heuristic as a kernel on the library's own random stream.  The
+        default WITHOUT constraints; with constraints only when the caller passes options["device_selection"] = True.  Reproducible for a seed, but the
+        restarts picked are not the host heuristic's: the Python path returns the same candidate only when handed the same picks
+        (options["log_picked"] records them).
+
+    options["device_rand"] draws the raw samples of the one-call form on the device (reproducible for a seed; not numpy's draws).  With constraints it
+    needs an explicit device_selection=True and no equality constraint - the device sampler rejects into the INEQUALITY constraints
+    (gabo_sphere_sample) and cannot draw ON an equality; otherwise the host sampler (`manifold.rand` / `rand_batch`, which the reference's constrained
+    examples replace by a sampler of feasible points) is used, still on the native path.  When the device sampler runs out of tries (a feasible set of
+    measure ~1e-3 of the sphere or less) the sweep warns once and continues in the two-call form with the host sampler.
+
+    solver.log: the keys of the Python path's single-launch solve that the driver knows, plus "final_constraints" (R x C constraint values at the final
+    iterates, equalities first; None without constraints) and "lds_resident" (which instantiation of the solve kernel ran)."""
     import ctypes
     import time
 
@@ -713,13 +743,30 @@ def _native_sweep_sphere(plan, acq_function, solver, num_restarts, raw_samples, 
     dim, R = int(man._n), int(num_restarts)
     cfg = _lib.SphereSweepConfig()
     cfg.acq = fused.sphere_acq_params()
-    mininner, maxinner, delta_bar, delta0, _ = default_limits(man)
+    mininner, maxinner, delta_bar, delta0, delta_cons = default_limits(man)
     cfg.delta_bar, cfg.delta0 = float(delta_bar), float(delta0)
     cfg.theta, cfg.kappa, cfg.mininner, cfg.maxinner = float(solver.theta), float(solver.kappa), int(mininner), int(maxinner)
     cfg.exact_hessian = 1 if plan["exact_hessian"] else 0
     cfg.rho_prime, cfg.rho_regularization = float(solver.rho_prime), float(solver.rho_regularization)
     cfg.mingradnorm, cfg.maxiter = float(solver.mingradnorm), int(solver.maxiter)
+    group, neq = plan.get("sphere_group"), int(plan.get("n_equalities", 0))
+    constrained = group is not None
+    C, cons, cons_ref = 0, None, None
+    if constrained:
+        kinds, indices, bounds, centres = group
+        C = len(kinds)
+        cons = _lib.SphereSweepConstraints()
+        cons.n_constraints, cons.n_equalities = C, neq
+        for k in range(C):
+            cons.kind[k], cons.index[k], cons.bound[k] = int(kinds[k]), int(indices[k]), float(bounds[k])
+        cons.centres = None if centres is None else centres.data_ptr()          # (the group keeps the tensor alive)
+        cons.n_centres = 0 if centres is None else int(centres.shape[0])
+        cons.strict, cons.delta_cons = (1 if solver.strict_constraints else 0), float(delta_cons)
+        cons_ref = ctypes.byref(cons)
     nonneg, eta, alpha = _selection(acq_function, options)
+    # with constraints the one-call form is opt-in (see above); the device sampler on top of it needs inequalities only
+    device_selection = bool(options.get("device_selection", True)) if not constrained else options.get("device_selection") is True
+    device_rand = bool(options.get("device_rand")) and (not constrained or (device_selection and neq == 0))
     time0 = time.time()
 
     def draw(total):          # the host samplers of _draw_raw_samples, same draws
@@ -732,48 +779,60 @@ def _native_sweep_sphere(plan, acq_function, solver, num_restarts, raw_samples, 
         return raw
 
     def workspace(total):
-        wsb = int(lib.gabo_sphere_sweep_workspace_bytes(dim, total, R))
+        wsb = int(lib.gabo_sphere_sweep_workspace_bytes_constrained(dim, total, R, C) if constrained else lib.gabo_sphere_sweep_workspace_bytes(dim, total, R))
         key = ("sphere", dev.index, stream)
         ws = _sweep_workspaces.get(key)
         if ws is None or ws.numel() < wsb:
             ws = _sweep_workspaces[key] = torch.empty(wsb, dtype=torch.uint8, device=dev)
         return ws, wsb
 
-    def result(ws, best, value, iters, cand_p, cost_p, it_p, picked_p=None, device_selection=False):
+    def result(ws, best, value, iters, cand_p, cost_p, it_p, cv_p, picked_p=None, device_selection=False):
         base = ws.data_ptr()
 
         def view(ptr, count, dtype):
             off = int(ptr.value) - base
             return ws[off:off + 8 * count].view(dtype)
         cands = view(cand_p, R * dim, torch.float64).reshape(R, dim)
+        lds = lib.gabo_sphere_tr_solve_lds_resident(ctypes.byref(cfg.acq), R, C)
         solver.log = {"iterations": int(iters.value), "per_restart_iterations": view(it_p, R, torch.int64).clone(),
                       "final_cost": view(cost_p, R, torch.float64).clone(), "final_gradnorm": None, "cost_evals": 0, "grad_evals": 0,
-                      "time": time.time() - time0, "one_launch_solve": True, "native_sweep": True, "device_selection": device_selection}
+                      "time": time.time() - time0, "one_launch_solve": True, "native_sweep": True, "device_selection": device_selection,
+                      "final_constraints": view(cv_p, R * C, torch.float64).reshape(R, C).clone() if (constrained and cv_p.value) else None,
+                      "lds_resident": bool(lds) if lds >= 0 else None}
         if picked_p is not None and options.get("log_picked"):
             solver.log["picked"] = view(picked_p, R, torch.int64).cpu().numpy().copy()
         return cands[int(best.value)].reshape(1, dim).clone()
 
     with torch.cuda.device(dev):
         stream = ops._stream_ptr(dev)
-        # ONE call, one wait (gabo_sphere_sweep_run): the selection heuristic as a kernel between the scoring and the solve (the SPD sweep's), the raw
-        # samples from the host sampler or - options["device_rand"] - drawn on the device.  Not for acquisition functions that can be negative, more raw
-        # samples than the kernel holds, or when it reports that the heuristic needs its random fall-backs: then the two-call path below runs.
-        if (options.get("device_selection", True) and nonneg and lib.gabo_spd_sweep_select_supported(raw_samples, R)):
+        # ONE call, one wait (gabo_sphere_sweep_run[_constrained]): the selection heuristic as a kernel between the scoring and the solve (the SPD
+        # sweep's), the raw samples from the host sampler or - device_rand - drawn on the device.  Not for acquisition functions that can be negative,
+        # more raw samples than the kernel holds, or when it reports that the heuristic needs its random fall-backs (or the constrained sampler that it
+        # ran out of tries): then the two-call path below runs.
+        if (device_selection and nonneg and lib.gabo_spd_sweep_select_supported(raw_samples, R)):
             total = raw_samples
             ws, wsb = workspace(total)
-            raw = None if options.get("device_rand") else draw(total)
+            raw = None if device_rand else draw(total)
             sample_seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64)) if raw is None else 0
             sel_seed = int(torch.randint(0, 2 ** 52, (1,)).item())
             best, iters, fallback = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0)
             value = ctypes.c_double(0.0)
-            cand_p, cost_p, it_p, picked_p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-            _lib.check(lib.gabo_sphere_sweep_run(ctypes.byref(cfg), total, R, None if raw is None else raw.ctypes.data, sample_seed, float(eta), float(alpha),
-                                                 sel_seed, ctypes.byref(best), ctypes.byref(value), ctypes.byref(iters), ctypes.byref(cand_p),
-                                                 ctypes.byref(cost_p), ctypes.byref(it_p), ctypes.byref(picked_p), ctypes.byref(fallback), ws.data_ptr(), wsb,
-                                                 stream), "gabo_sphere_sweep_run")
+            cand_p, cost_p, it_p, picked_p, cv_p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+            head = (ctypes.byref(cfg), total, R, None if raw is None else raw.ctypes.data, sample_seed, float(eta), float(alpha), sel_seed,
+                    ctypes.byref(best), ctypes.byref(value), ctypes.byref(iters), ctypes.byref(cand_p), ctypes.byref(cost_p), ctypes.byref(it_p),
+                    ctypes.byref(picked_p), ctypes.byref(fallback))
+            if constrained:
+                _lib.check(lib.gabo_sphere_sweep_run_constrained(*head, cons_ref, ctypes.byref(cv_p), ws.data_ptr(), wsb, stream),
+                           "gabo_sphere_sweep_run_constrained")
+            else:
+                _lib.check(lib.gabo_sphere_sweep_run(*head, ws.data_ptr(), wsb, stream), "gabo_sphere_sweep_run")
             ops.check_deferred()
             if not fallback.value:
-                return result(ws, best, value, iters, cand_p, cost_p, it_p, picked_p, True)
+                return result(ws, best, value, iters, cand_p, cost_p, it_p, cv_p, picked_p, True)
+            if fallback.value == 2 and not getattr(_native_sweep_sphere, "_warned_exhausted", False):
+                _native_sweep_sphere._warned_exhausted = True
+                warnings.warn(f"the device sampler found no feasible point for some raw sample in {_lib.GABO_SPHERE_SAMPLE_MAX_TRIES} tries (the "
+                              "inequality constraints leave too small a part of the sphere): the raw samples come from manifold.rand on the host")
         picked = None
         for attempt in range(1, 5):
             total = raw_samples * attempt
@@ -795,15 +854,18 @@ def _native_sweep_sphere(plan, acq_function, solver, num_restarts, raw_samples, 
         idx = np.ascontiguousarray(picked, dtype=np.int64)
         best, iters = ctypes.c_int64(0), ctypes.c_int64(0)
         value = ctypes.c_double(0.0)
-        cand_p, cost_p, it_p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-        _lib.check(lib.gabo_sphere_sweep_solve(ctypes.byref(cfg), idx.ctypes.data, R, total, ctypes.byref(best), ctypes.byref(value), ctypes.byref(iters),
-                                               ctypes.byref(cand_p), ctypes.byref(cost_p), ctypes.byref(it_p), ws.data_ptr(), wsb, stream),
-                   "gabo_sphere_sweep_solve")
+        cand_p, cost_p, it_p, cv_p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        head = (ctypes.byref(cfg), idx.ctypes.data, R, total, ctypes.byref(best), ctypes.byref(value), ctypes.byref(iters), ctypes.byref(cand_p),
+                ctypes.byref(cost_p), ctypes.byref(it_p))
+        if constrained:
+            _lib.check(lib.gabo_sphere_sweep_solve_constrained(*head, cons_ref, ctypes.byref(cv_p), ws.data_ptr(), wsb, stream),
+                       "gabo_sphere_sweep_solve_constrained")
+        else:
+            _lib.check(lib.gabo_sphere_sweep_solve(*head, ws.data_ptr(), wsb, stream), "gabo_sphere_sweep_solve")
+    out = result(ws, best, value, iters, cand_p, cost_p, it_p, cv_p)
     if options.get("log_picked"):
-        out = result(ws, best, value, iters, cand_p, cost_p, it_p)
         solver.log["picked"] = idx.copy()
-        return out
-    return result(ws, best, value, iters, cand_p, cost_p, it_p)
+    return out
 
 
 def gen_batch_initial_conditions_manifold(acq_function, manifold, bounds, q, num_restarts, raw_samples,

@@ -1819,6 +1819,46 @@ def sphere_constraints_eval(x, kinds, indices, bounds, centres=None, want_grad=T
     return (values, grads) if want_grad else values
 
 
+def sphere_sample(count, dim, seed, constraints=None, device=None):
+    """count points uniform on S^(dim-1) inside the library's INEQUALITY constraints, drawn on the device by rejection (gabo_sphere_sample: try t of
+    sample i is item i + t * count of the library's Philox stream `seed`; without constraints the stream's first count points).  constraints: None, a
+    list of the library's sphere constraints (functools.partial with every parameter by keyword) or the (kinds, indices, bounds, centres) that
+    sphere_constraints_utils_torch.builtin_sphere_group packs.  Returns (points count x dim, exhausted): exhausted = some sample was still infeasible
+    after GABO_SPHERE_SAMPLE_MAX_TRIES tries and holds its last try."""
+    import ctypes
+    lib = _lib.load()
+    dev = _device_for() if device is None else torch.device(device)
+    count, dim = int(count), int(dim)
+    if constraints is None or len(constraints) == 0:
+        kinds, indices, bounds, centres = [], [], [], None
+    elif len(constraints) == 4 and isinstance(constraints[0], (list, tuple)) and not callable(constraints[0]):
+        kinds, indices, bounds, centres = constraints
+    else:
+        from .Riemannian_utils.sphere_constraints_utils_torch import builtin_sphere_group
+        group = builtin_sphere_group(list(constraints), dim, dev)
+        if group is None:
+            raise ValueError("sphere_sample: every constraint must be one of the library's sphere constraints with its parameters bound by keyword "
+                             "(at most 8 of them)")
+        kinds, indices, bounds, centres = group
+    nc = len(kinds)
+    if len(indices) != nc or len(bounds) != nc:
+        raise ValueError("kinds, indices and bounds: one entry per constraint")
+    if centres is not None:
+        centres = _prep(centres, dev).contiguous()
+        if centres.dim() != 2 or centres.shape[1] != dim:
+            raise ValueError("centres: n_centres x dim")
+    out = torch.empty(count, dim, dtype=torch.float64, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    ck = (ctypes.c_int * max(nc, 1))(*kinds)
+    ci = (ctypes.c_int * max(nc, 1))(*indices)
+    cb = (ctypes.c_double * max(nc, 1))(*bounds)
+    with _on(dev):
+        _lib.check(lib.gabo_sphere_sample(out.data_ptr(), count, dim, int(seed) & 0xFFFFFFFFFFFFFFFF, nc, 0, ck, ci, cb,
+                                          None if centres is None else centres.data_ptr(), 0 if centres is None else int(centres.shape[0]),
+                                          flag.data_ptr(), _stream_ptr(dev)), "gabo_sphere_sample")
+    return out, bool(flag.item())
+
+
 def sphere_manifold_op(op, x, u, v=None, w=None):
     """Batched sphere-manifold operation (one of _lib.GABO_SPH_*) on (..., dim) tensors."""
     lib = _lib.load()

@@ -697,6 +697,49 @@ int gabo_sphere_sweep_run(const gabo_sphere_sweep_config* cfg, int64_t count, in
                                      int* fallback_host,
                           void* workspace, size_t workspace_bytes, gabo_stream_t stream);
 
+/* The same sweep with the library's own sphere constraints (GABO_SPHERE_CONSTRAINT_*, at most 8, equalities first) evaluated inside the solve launch
+ * (gabo_sphere_tr_solve_constrained): what the reference's constrained sphere examples run when their constraints are the library functions.
+ * kind / index / bound as gabo_sphere_tr_solve_constrained takes them; centres: n_centres x dim on the device; strict != 0: the strict solver;
+ * delta_cons: the distance at which the linearised constraints truncate a tCG step.  The set is checked on the host before any launch
+ * (GABO_ERR_ARG: more than 8, more equalities than constraints, an unknown kind, a coordinate outside [0, dim), a ball outside [0, n_centres) or
+ * without centres). */
+typedef struct {
+    int n_constraints, n_equalities;   /* equalities first */
+    int kind[8], index[8];
+    double bound[8];
+    const double* centres;             /* device pointer */
+    int n_centres;
+    int strict;
+    double delta_cons;
+} gabo_sphere_sweep_constraints;
+/* The workspace of the _constrained calls: the layout of gabo_sphere_sweep_workspace_bytes with restarts x n_constraints doubles for the final constraint
+ * values and the trust-region workspace of gabo_sphere_tr_workspace_bytes(restarts, dim, n_constraints) at its end.  Everything in front of those two
+ * blocks sits where the unconstrained layout has it, so gabo_sphere_sweep_score (which needs no constraints) serves this workspace as it is. */
+size_t gabo_sphere_sweep_workspace_bytes_constrained(int dim, int64_t max_raw, int64_t restarts, int n_constraints);
+/* gabo_sphere_sweep_solve on that workspace; one more launch (gabo_sphere_constraints_eval, values only) in front of the read-back leaves the
+ * constraints at the final iterates in the workspace: *constraint_values_dev (may be NULL), restarts x n_constraints, NULL without constraints. */
+int gabo_sphere_sweep_solve_constrained(const gabo_sphere_sweep_config* cfg, const int64_t* picked_host, int64_t restarts, int64_t max_raw,
+                                        int64_t* best_index_host, double* best_value_host, int64_t* max_iterations_host, double** candidates_dev,
+                                        double** cost_dev, int64_t** iterations_dev, const gabo_sphere_sweep_constraints* constraints,
+                                        double** constraint_values_dev, void* workspace, size_t workspace_bytes, gabo_stream_t stream);
+/* gabo_sphere_sweep_run on that workspace.  raw_points_host NULL: the raw samples are drawn INSIDE the inequality constraints (gabo_sphere_sample on the
+ * stream `sample_seed`); with an equality constraint that is GABO_ERR_ARG - the caller's host sampler draws on it.  *fallback_host = 1 as for
+ * gabo_sphere_sweep_run; = 2: the sampler ran out of tries for some sample - nothing else is valid and the caller samples on the host. */
+int gabo_sphere_sweep_run_constrained(const gabo_sphere_sweep_config* cfg, int64_t count, int64_t restarts, const double* raw_points_host,
+                                      uint64_t sample_seed, double eta, double alpha, uint64_t select_seed, int64_t* best_index_host,
+                                      double* best_value_host, int64_t* max_iterations_host, double** candidates_dev, double** cost_dev,
+                                      int64_t** iterations_dev, int64_t** picked_dev, int* fallback_host,
+                                      const gabo_sphere_sweep_constraints* constraints, double** constraint_values_dev, void* workspace,
+                                      size_t workspace_bytes, gabo_stream_t stream);
+/* count points uniform on S^(dim-1) inside the library's INEQUALITY constraints (all strictly positive), by rejection on the library's Philox stream:
+ * try t of sample i is item i + t * count of the stream gabo_sphere_sweep_run draws from (key `seed`, Box-Muller, normalised), so the draw is rows of
+ * ONE unconstrained stream and without constraints it is that stream's first count points.  At most GABO_SPHERE_SAMPLE_MAX_TRIES tries per sample; a
+ * sample that exhausts them keeps its last try and sets *exhausted_dev (device int, written 0 or 1).  out: count x dim on the device; the constraint
+ * arrays as gabo_sphere_tr_solve_constrained takes them; n_equalities > 0 is GABO_ERR_ARG. */
+#define GABO_SPHERE_SAMPLE_MAX_TRIES 256
+int gabo_sphere_sample(double* out, int64_t count, int dim, uint64_t seed, int n_constraints, int n_equalities, const int* kind, const int* index,
+                       const double* bound, const double* centres, int n_centres, int* exhausted_dev, gabo_stream_t stream);
+
 /* Batched sphere-manifold operations, x/u/v/w/out: n x dim (GABO_SPH_DIST writes n scalars).
  *   GABO_SPH_PROJ   out = U - <X,U> X        [3P] Sphere.proj = egrad2rgrad; transp(X,Y,U) = proj(Y,U)
  *   GABO_SPH_RETR   out = (X+U)/|X+U|        [3P] Sphere.retr  (robust_trust_regions.py:228)
