@@ -635,11 +635,12 @@ class BatchedTrustRegions:
             from ..Riemannian_utils.spd_constraints_utils_torch import builtin_constraint, builtin_lift
             builtins = [builtin_constraint(c) for c in cons]
             # no constraint needs a host callable (none, or eigenvalue bounds built with functools.partial as in the reference examples)
-            solve_ok = d <= 8 and neq == 0 and all(b is not None for b in builtins)
+            solve_ok = neq == 0 and all(b is not None for b in builtins)
             lift = builtin_lift(builtins) if solve_ok else None      # the nested kinds' mapping (one for all of them)
             solve_ok = solve_ok and lift is not False
             if solve_ok:
-                # (the library's own word: e.g. no single-launch form of the log-Euclidean surrogate at d = 7, 8 beyond what its LDS holds)
+                # (the library's own word, not a dimension written down here: today no single launch above d = 8 - it refuses those by its own
+                # check - and e.g. no single-launch form of the log-Euclidean surrogate at d = 7, 8 beyond what its LDS holds)
                 import ctypes
                 solve_ok = bool(_library().gabo_spd_tr_solve_supported(ctypes.byref(fused.acq_params()), R, d, ncons,
                                                                        0 if lift is None else int(lift[0].shape[0])))

@@ -452,8 +452,8 @@ def _native_sweep_plan(acq_function, manifold, solver, q, num_restarts, raw_samp
             and isinstance(solver, BatchedTrustRegions) and not solver.use_rand and solver.maxtime >= 1000
             and solver.trace is None and not equality_constraints):
         return None
-    if not (isinstance(manifold, PositiveDefinite) and 2 <= manifold._n <= 8):
-        return None
+    if not (isinstance(manifold, PositiveDefinite) and manifold._n >= 2):
+        return None       # (how far up the drivers go is the library's to say: gabo_spd_tr_solve_supported below)
     device_rand = bool(options.get("device_rand")) and hasattr(manifold, "rand_batch_device")
     if device_rand and not (type(manifold).rand_batch_device is PositiveDefinite.rand_batch_device and "rand_batch_device" not in vars(manifold)
                             and hasattr(manifold, "min_eig") and hasattr(manifold, "max_eig")):

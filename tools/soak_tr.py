@@ -4,7 +4,9 @@ bounds (none / max / box; plain or strict), random starts - every outer iteratio
 record, gabo_tr_solve_record) and of the propose / update launches walked against the generic path's trace: radius (exact), tCG stop reason,
 iterate within `atol`.  Prints the share of restart-iterations that agree and where runs part.
 
-    python tools/soak_tr.py [--cases 60] [--seed 0]
+    python tools/soak_tr.py [--cases 60] [--seed 0] [--dims 9,10,11,12]
+
+--dims restricts the soak to S^d_++ cases of those dimensions (above d = 8: the affine-invariant surrogate, the only one with device plans there).
 """
 import argparse
 import functools
@@ -51,10 +53,12 @@ def walk(ref, got, atol):
     return total, agree, parted
 
 
-def spd_case(rng):
-    d = int(rng.choice([2, 3, 4, 5, 6, 7, 8]))
+def spd_case(rng, dims=(2, 3, 4, 5, 6, 7, 8)):
+    d = int(rng.choice(list(dims)))
     n = int(rng.integers(4, 60))
     flav = int(rng.integers(0, 5))          # 0, 1: affine-invariant; 2, 3: log-Euclidean; 4: Frobenius
+    if d > 8:
+        flav = 0
     le, frob = flav in (2, 3), flav == 4
     q = np.linalg.qr(rng.standard_normal((n, d, d)))[0]
     Xm = np.einsum("nab,nb,ncb->nac", q, rng.uniform(0.2, 3.0, (n, d)), q)
@@ -101,6 +105,7 @@ def main():
     ap.add_argument("--cases", type=int, default=60)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--atol", type=float, default=1e-6)
+    ap.add_argument("--dims", type=lambda v: tuple(int(k) for k in v.split(",")), default=None, help="S^d_++ cases of these dimensions only")
     ap.add_argument("--only", type=int, default=-1, help="run this case alone (the generator is advanced through the earlier ones)")
     ap.add_argument("--no-record", action="store_true", help="(with --only) the single-launch solve without its record")
     a = ap.parse_args()
@@ -109,7 +114,10 @@ def main():
     worst = []
     ops.set_error_checking(False)
     for c in range(a.cases):
-        desc, acq, man, x0, cons, strict, kw = (spd_case if c % 3 else sphere_case)(rng)
+        if a.dims:
+            desc, acq, man, x0, cons, strict, kw = spd_case(rng, a.dims)
+        else:
+            desc, acq, man, x0, cons, strict, kw = (spd_case if c % 3 else sphere_case)(rng)
         if a.only >= 0 and c != a.only:
             continue
         traces = {}
