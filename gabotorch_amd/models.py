@@ -326,9 +326,8 @@ class SingleTaskGP(torch.nn.Module):
         """(E, theta_fn, outputscale_fn) when the covariance is [ScaleKernel of] one of the path's plain kernels, all of which
         are exp(-theta * E) with E = d^2 or d fixed during a fit; None for anything else (nested kernels carry extra
         parameters inside the distance, batched hyper-parameters, more than GABO_GP_MLL_LARGE_MAX_N points)."""
-        from . import _lib, ops
-        from .kernel_utils import kernels_sphere as ksph
-        from .kernel_utils import kernels_spd as kspd
+        from . import _lib
+        from .kernel_utils import kernel_parameters
         cm = self.covar_module
         base = getattr(cm, "base_kernel", None)
         if base is None:
@@ -340,28 +339,17 @@ class SingleTaskGP(torch.nn.Module):
         x = self.train_x
         if x.dim() != 2 or not 1 <= x.shape[0] <= _lib.GABO_GP_MLL_LARGE_MAX_N:
             return None
-        kind = type(base)
-        dist_mode = _lib.GABO_OUT_DISTANCE
-        beta_fn = lambda: base.beta.double().reshape(())                                       # noqa: E731
-        ls_fn = lambda: 1.0 / base.lengthscale.double().reshape(()) ** 2                       # noqa: E731
-        if kind in (kspd.SpdAffineInvariantGaussianKernel, kspd.SpdAffineInvariantLaplaceKernel):
-            dist, theta_fn = (lambda v: ops.spd_ai_pairwise(v, v, 1.0, dist_mode)), beta_fn
-            power = 2 if kind is kspd.SpdAffineInvariantGaussianKernel else 1
-        elif kind is kspd.SpdFrobeniusGaussianKernel:
-            dist, theta_fn, power = (lambda v: ops.frobenius_pairwise(v, v, 1.0, dist_mode)), ls_fn, 2
-        elif kind is kspd.SpdLogEuclideanGaussianKernel:
-            dist, theta_fn, power = (lambda v: ops.frobenius_pairwise(*(2 * (ops.spd_logm_mandel(v),)), 1.0, dist_mode)), ls_fn, 2
-        elif kind is ksph.SphereGaussianKernel:
-            dist, theta_fn, power = (lambda v: ops.sphere_pairwise(v, v, 1.0, dist_mode)), beta_fn, 2
-        elif kind is ksph.SphereLaplaceKernel:
-            dist, theta_fn, power = (lambda v: ops.sphere_pairwise(v, v, 1.0, dist_mode)), ls_fn, 1
-        else:
+        try:                                               # (the table of the plain kernels and their exponents is stated there, once)
+            theta_of = kernel_parameters.parameter_map(base)
+        except TypeError:
             return None
+        if theta_of.parameter == "beta":
+            theta_fn = lambda: theta_of(base.beta.double().reshape(()))                        # noqa: E731
+        else:
+            theta_fn = lambda: theta_of(base.lengthscale.double().reshape(()))                 # noqa: E731
         if theta_fn().numel() != 1:
             return None
-        with torch.no_grad():
-            d = dist(x.to(ops._device_for(x)))
-            e = (d * d if power == 2 else d).contiguous()
+        e = kernel_parameters.exponent_matrix(base, x)[0]
         return e, theta_fn, os_fn
 
     def _fast_mll_closure(self):

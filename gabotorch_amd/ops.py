@@ -1362,6 +1362,40 @@ def gp_mll_gram(k, y, outputscale, noise, mean, want_w=True):
     return out, w
 
 
+def gram_extreme_eigenvalues(e, thetas):
+    """gabo_gram_extreme_eig: {lambda_min, lambda_max} of K = exp(-theta * e), entry by entry, for every matrix of e and every theta in one
+    launch (the kernel-parameter studies of examples/kernels/*/..._kernel_parameters.py; kernel_utils.kernel_parameters builds e).
+    e: (..., n, n) fp64 on a HIP device, symmetric (the lower triangle and the diagonal are read), n <= GABO_GRAM_EIG_MAX_N;
+    thetas: (P,) tensor or sequence.  -> (..., P, 2) on e's device.  A non-finite entry of a matrix or a non-finite theta gives NaN for
+    the pairs it touches, no error.  The workspace is allocated here; no host synchronisation."""
+    lib = _lib.load()
+    if not torch.is_tensor(e) or not e.is_cuda or e.dtype != torch.float64:
+        raise ValueError("gram_extreme_eigenvalues: e must be an fp64 tensor on a HIP device")
+    if e.dim() < 2 or e.shape[-1] != e.shape[-2]:
+        raise ValueError(f"gram_extreme_eigenvalues: e must be (..., n, n), got {tuple(e.shape)}")
+    dev, n = e.device, e.shape[-1]
+    if not 1 <= n <= _lib.GABO_GRAM_EIG_MAX_N:
+        raise ValueError(f"gram_extreme_eigenvalues: n = {n} outside 1 ... {_lib.GABO_GRAM_EIG_MAX_N}")
+    th = thetas if torch.is_tensor(thetas) else torch.as_tensor(thetas, dtype=torch.float64)
+    if th.dim() != 1 or th.numel() < 1:
+        raise ValueError(f"gram_extreme_eigenvalues: thetas must be (P,) with P >= 1, got {tuple(th.shape)}")
+    th = th.to(device=dev, dtype=torch.float64).contiguous()
+    bshape, nt = tuple(e.shape[:-2]), th.numel()
+    nb = 1
+    for s in bshape:
+        nb *= s
+    if nb < 1:
+        raise ValueError(f"gram_extreme_eigenvalues: empty batch {tuple(e.shape)}")
+    ec = e.contiguous()
+    out = torch.empty(bshape + (nt, 2), dtype=torch.float64, device=dev)
+    wsb = int(lib.gabo_gram_extreme_eig_workspace_bytes(nb, n, nt))
+    ws = torch.empty(wsb // 8, dtype=torch.float64, device=dev) if wsb else None
+    with _on(dev):
+        _lib.check(lib.gabo_gram_extreme_eig(ec.data_ptr(), nb, n, th.data_ptr(), nt, out.data_ptr(), None if ws is None else ws.data_ptr(),
+                                             wsb, _stream_ptr(dev)), "gabo_gram_extreme_eig")
+    return out
+
+
 def spd_acq_prepare_train(train_mandel):
     """Entry-major Cholesky factors of the training matrices for spd_acq_eval (d_vec x n)."""
     lib = _lib.load()

@@ -287,6 +287,26 @@ int gabo_gp_mll_large(const double* e, const double* y, int64_t n, double theta,
                       double* out, double* w, void* workspace, size_t workspace_bytes, gabo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Extreme eigenvalues of the kernel matrices of a kernel-parameter study, all (point set, parameter) pairs in one launch
+ * (examples/kernels/spd/spd_gaussian_kernel_parameters.py:84-125 and examples/kernels/sphere/sphere_gaussian_kernel_parameters.py:62-112:
+ * per pair one kernel.forward and one np.linalg.eig on the host, of which the minimum is kept).
+ *   e: batch symmetric n x n matrices (row-major; the lower triangle and the diagonal are read) with E = d^2 or d as for gabo_gp_mll,
+ *   thetas: n_thetas parameters ON THE DEVICE;  K = exp(-thetas[p] * e[b]) entry by entry, the diagonal as given.
+ *   out[(b * n_thetas + p) * 2 + {0, 1}] = {lambda_min(K), lambda_max(K)}.
+ * A non-finite entry of e[b] or a non-finite thetas[p] gives NaN in both outputs of that pair; it is no error.  (So does an entry of K
+ * above 1e150, which a negative theta can produce: its square is not representable.)
+ * One workgroup per pair: Householder tridiagonalisation of the lower triangle in place, then bisection on Sturm counts
+ * (csrc/gram_eig.hip).  The triangle lives in LDS for n <= GABO_GRAM_EIG_LDS_MAX_N (no workspace: *_workspace_bytes is 0 and
+ * workspace may be NULL) and in the workspace beyond: batch * n_thetas * n (n + 1) / 2 doubles.
+ * GABO_ERR_DIM for n > GABO_GRAM_EIG_MAX_N; GABO_ERR_ARG for a null e / thetas / out, n, batch or n_thetas < 1, more than 2^31 - 1
+ * pairs or a workspace smaller than *_workspace_bytes (0 for such arguments) - all before any HIP call. */
+#define GABO_GRAM_EIG_MAX_N 1024
+#define GABO_GRAM_EIG_LDS_MAX_N 192
+size_t gabo_gram_extreme_eig_workspace_bytes(int64_t batch, int64_t n, int64_t n_thetas);
+int gabo_gram_extreme_eig(const double* e, int64_t batch, int64_t n, const double* thetas, int64_t n_thetas,
+                          double* out, void* workspace, size_t workspace_bytes, gabo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * One evaluation of the surrogate-fit objective of HD-GaBO with its gradient, as one HOST call (it returns with the numbers):
  * the marginal log likelihood of ScaleKernel(NestedSpdLogEuclideanGaussianKernel) at a projection matrix W and scalar hyper-parameters.
  * Replaces the closure fit_gpytorch_manifold differentiates by autograd   manifold_optimization/manifold_gp_fit.py:54-222
