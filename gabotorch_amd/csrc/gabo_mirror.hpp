@@ -36,4 +36,15 @@ __host__ __device__ inline int64_t sym_chunks_of(int64_t cg, int cols, int rows,
     return cnt < row_chunks ? cnt : row_chunks;
 }
 
+// Enumeration of the square tiles on and below the diagonal, row by row: tile t is (bi, bj <= bi) with t = bi (bi + 1) / 2 + bj.  For the
+// kernels that produce a lower tile and store its mirror image themselves (gp_posterior.hip) instead of running mirror_upper_kernel
+// afterwards.  Exact for t < 2^52 (the square root is only a first guess).
+__host__ __device__ inline void lower_tile_of(int64_t t, int64_t& bi, int64_t& bj) {
+    int64_t r = (int64_t)((__builtin_sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (r * (r + 1) / 2 > t) --r;
+    while ((r + 1) * (r + 2) / 2 <= t) ++r;
+    bi = r;
+    bj = t - r * (r + 1) / 2;
+}
+
 }  // namespace gabo

@@ -21,6 +21,93 @@ class BadInitialCandidatesWarning(RuntimeWarning):
     pass
 
 
+class MultivariateNormal:
+    """gpytorch.distributions.MultivariateNormal as the reference's GP-regression demos read it (examples/kernels/spd/spd_kernels.py:168-174)
+    [3P]: mean, variance, stddev, covariance_matrix, confidence_region(), sample() / rsample() - what `model(x_test)` returns.  One test
+    set (mean (m,), covariance m x m, dense); nothing here is differentiable.  The factor behind the samples is gpytorch's psd_safe_cholesky
+    ladder for doubles (ops.mvn_sample): `jitter_used` tells which rung it took."""
+
+    def __init__(self, mean, covariance_matrix, variance=None):
+        if mean.dim() != 1 or covariance_matrix.dim() != 2 or tuple(covariance_matrix.shape) != (mean.shape[0], mean.shape[0]):
+            raise ValueError(f"MultivariateNormal: mean {tuple(mean.shape)} and covariance {tuple(covariance_matrix.shape)}: one test set, (m,) and m x m")
+        self._mean, self._cov, self._var = mean, covariance_matrix, variance
+        self._factor = None                       # (scale_tril, rung) of the last factorisation
+
+    @property
+    def mean(self):
+        return self._mean
+
+    loc = mean
+
+    @property
+    def covariance_matrix(self):
+        return self._cov
+
+    @property
+    def variance(self):
+        """the diagonal of the covariance, clamped at 0 (rounding can leave a tiny negative entry where the posterior pins f)"""
+        v = torch.diagonal(self._cov) if self._var is None else self._var
+        return v.clamp_min(0.0)
+
+    @property
+    def stddev(self):
+        return self.variance.sqrt()
+
+    @property
+    def event_shape(self):
+        return self._mean.shape
+
+    def confidence_region(self):
+        """(mean - 2 stddev, mean + 2 stddev)"""
+        s2 = 2.0 * self.stddev
+        return self._mean - s2, self._mean + s2
+
+    def _draw(self, sample_shape, base_samples, seed):
+        dev = _ops._device_for(self._cov)
+        out, tril, rung = _ops.mvn_sample(self._mean.to(dev), self._cov.to(dev), sample_shape, seed=seed, base_samples=base_samples,
+                                          return_scale_tril=True)
+        self._factor = (tril, rung)
+        return out
+
+    def sample(self, sample_shape=torch.Size(), base_samples=None, seed=None):
+        """sample_shape + (m,) draws mean + L z on the distribution's device; z = base_samples (sample_shape + (m,)) when given, else the
+        library's counter-based normals for `seed` (None: a seed from numpy's global generator)."""
+        return _ops._out(self._draw(tuple(sample_shape), base_samples, seed), self._mean.device)
+
+    rsample = sample
+
+    @property
+    def scale_tril(self):
+        """L with L L^T = covariance + jitter_used * I, lower triangular"""
+        if self._factor is None:
+            self._draw((0,), None, 0)
+        return _ops._out(self._factor[0], self._mean.device)
+
+    @property
+    def jitter_used(self):
+        """what the factorisation added to the diagonal: an entry of _lib.GABO_MVN_JITTER_LADDER (reads one word back from the device)"""
+        if self._factor is None:
+            self._draw((0,), None, 0)
+        _ops.check_deferred()
+        return _l.GABO_MVN_JITTER_LADDER[int(self._factor[1])]
+
+
+def _joint_posterior(base_kernel, outputscale, train_x, linv, alpha, mean, X):
+    """the distribution of the latent f at the test set X (m x d_vec): k* and k** from the kernel's own launches, then ops.gp_posterior_joint"""
+    if not torch.is_tensor(X) or X.dim() != 2:
+        raise ValueError(f"forward: X must be one test set, m x d_vec, got {tuple(getattr(X, 'shape', ()))}; batches of candidates go through posterior()")
+    with torch.no_grad():
+        X = X.double()
+        dev = _ops._device_for(linv, X)
+        kstar = base_kernel.forward(X, train_x.to(X.device)).double()
+        kss = base_kernel.forward(X, X).double()
+        if kstar.dim() != 2 or kss.dim() != 2:
+            raise ValueError("forward: the kernel returned a batch of matrices; a joint posterior is over one test set")
+        mu, var, cov = _ops.gp_posterior_joint(kstar.to(dev), kss.to(dev), linv.to(dev), alpha.to(dev), float(mean), float(outputscale))
+        out_dev = X.device
+        return MultivariateNormal(_ops._out(mu, out_dev), _ops._out(cov, out_dev), _ops._out(var, out_dev))
+
+
 class ExactGP(torch.nn.Module):
     def __init__(self, train_x, train_y, base_kernel, outputscale=1.0, noise=1e-2, mean=None):
         super().__init__()
@@ -96,6 +183,13 @@ class ExactGP(torch.nn.Module):
         v = ks @ Li.transpose(-1, -2)                                           # b x n  = (L^-1 ks^T)^T
         var = kss.reshape(b) - (v * v).sum(-1)
         return mean, var
+
+    def forward(self, X):
+        """`model(x_test)`: the joint posterior of the latent f (no observation noise) over the test set X (m x d_vec) as a
+        MultivariateNormal - mean, covariance and samples from the device (ops.gp_posterior_joint, ops.mvn_sample).  No autograd."""
+        Linv, alpha = self._train_cache()
+        _ops.check_deferred()
+        return _joint_posterior(self.base_kernel, self.outputscale, self.train_x, Linv, alpha, self.mean, X)
 
 
 class ExpectedImprovement(torch.nn.Module):
@@ -532,6 +626,21 @@ class SingleTaskGP(torch.nn.Module):
         mean = mu.to(ks.device) + ks @ ad
         v = ks @ Li.transpose(-1, -2)
         return mean, kss - (v * v).sum(-1)
+
+    def forward(self, X):
+        """`preds = model(x_test)` of the reference's GP-regression demos (examples/kernels/spd/spd_kernels.py:168): the joint posterior of
+        the latent f (no observation noise) over the test set X (m x d_vec) as a MultivariateNormal.  The kernel matrices come from the
+        covariance module's own launches (any kernel of the library), the rest from ops.gp_posterior_joint.  Freezes the hyper-parameters
+        like posterior(); no autograd through the prediction."""
+        Linv, alpha, mu = self._ensure_cache()
+        from . import ops as _ops
+        _ops.check_deferred()
+        cm = self.covar_module
+        if hasattr(cm, "base_kernel") and type(cm).__name__ == "ScaleKernel" and cm.raw_outputscale.numel() == 1:
+            base, outputscale = cm.base_kernel, float(cm.outputscale.detach())
+        else:
+            base, outputscale = cm, 1.0
+        return _joint_posterior(base, outputscale, self.train_x, Linv, alpha, float(mu), X)
 
 
 def fit_gpytorch_model(model, maxiter=200, fast=True):

@@ -1396,6 +1396,119 @@ def gram_extreme_eigenvalues(e, thetas):
     return out
 
 
+def gp_posterior_joint(kstar, kss, linv, alpha, mean, outputscale, inplace=True):
+    """Joint posterior of the latent f over a test set in two launches (gabo_gp_posterior_joint): kstar m x n and kss m x m BASE kernel values
+    (test x train, test x test; the lower triangle and the diagonal of kss are read), linv = L^-1 with L L^T = outputscale k + noise I and
+    alpha = Ky^-1 (y - mean) from the prediction cache -> (mean (m,), variance (m,), covariance m x m, exactly symmetric; its diagonal is
+    the variance bit for bit).  kss is overwritten with the covariance and returned unless inplace=False.  All tensors fp64 on one HIP
+    device, n <= GABO_GP_MLL_LARGE_MAX_N; dense m x m memory.  No host synchronisation."""
+    lib = _lib.load()
+    for name, t in (("kstar", kstar), ("kss", kss), ("linv", linv), ("alpha", alpha)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float64:
+            raise ValueError(f"gp_posterior_joint: {name} must be an fp64 tensor on a HIP device")
+    if kstar.dim() != 2 or kss.dim() != 2:
+        raise ValueError(f"gp_posterior_joint: kstar must be m x n and kss m x m (one test set), got {tuple(kstar.shape)} and {tuple(kss.shape)}")
+    dev = kstar.device
+    m, n = kstar.shape
+    if tuple(kss.shape) != (m, m) or tuple(linv.shape) != (n, n) or alpha.numel() != n:
+        raise ValueError(f"gp_posterior_joint: kstar {tuple(kstar.shape)}, kss {tuple(kss.shape)}, linv {tuple(linv.shape)} and alpha "
+                         f"{tuple(alpha.shape)} do not belong together")
+    if not (1 <= m <= _lib.GABO_GP_POSTERIOR_MAX_M and 1 <= n <= _lib.GABO_GP_MLL_LARGE_MAX_N):
+        raise ValueError(f"gp_posterior_joint: m = {m}, n = {n} outside 1 ... {_lib.GABO_GP_POSTERIOR_MAX_M}, 1 ... {_lib.GABO_GP_MLL_LARGE_MAX_N}")
+    ks, li, al = kstar.contiguous(), linv.contiguous(), alpha.contiguous()
+    cov = kss if (inplace and kss.is_contiguous()) else kss.clone(memory_format=torch.contiguous_format)
+    _require(dev, kstar=ks, kss=cov, linv=li, alpha=al)
+    out = torch.empty(2, m, dtype=torch.float64, device=dev)
+    wsb = int(lib.gabo_gp_posterior_joint_workspace_bytes(m, n))
+    ws = torch.empty(wsb // 8, dtype=torch.float64, device=dev)
+    with _on(dev):
+        _lib.check(lib.gabo_gp_posterior_joint(ks.data_ptr(), cov.data_ptr(), li.data_ptr(), al.data_ptr(), m, n, float(mean), float(outputscale),
+                                               out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), wsb, _stream_ptr(dev)),
+                   "gabo_gp_posterior_joint")
+    if inplace and cov is not kss:
+        kss.copy_(cov)
+        cov = kss
+    return out[0], out[1], cov
+
+
+_MVN_MESSAGE = ("gabo_mvn_sample: the covariance matrix is not positive definite (no Cholesky factor with a jitter of 0, 1e-8, 1e-7 or 1e-6 "
+                "on the diagonal)")
+
+
+def _mvn_seed(seed):
+    if seed is None:
+        import numpy as np
+        seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64))
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def mvn_base_samples(samples, m, seed, device=None):
+    """samples x m standard normals of the stream gabo_mvn_sample draws from when it is given no base samples (Philox, key = seed, item = sample
+    index, draw k -> coordinates 2k and 2k + 1, stream tag "mvnz"): the same seed gives the same normals here and there."""
+    lib = _lib.load()
+    dev = _device_for() if device is None else torch.device(device)
+    samples, m = int(samples), int(m)
+    if samples < 0 or m < 1:
+        raise ValueError(f"mvn_base_samples: samples = {samples}, m = {m}")
+    out = torch.empty(samples, m, dtype=torch.float64, device=dev)
+    with _on(dev):
+        _lib.check(lib.gabo_mvn_base_samples(out.data_ptr(), samples, m, _mvn_seed(seed), _stream_ptr(dev)), "gabo_mvn_base_samples")
+    return out
+
+
+def mvn_sample(mean, cov, sample_shape=(), seed=None, base_samples=None, return_scale_tril=False):
+    """Draws from N(mean, cov): sample_shape + (m,) on cov's device, out = mean + L z with L L^T = cov + j I for the first j of
+    GABO_MVN_JITTER_LADDER that factors (gpytorch's psd_safe_cholesky for doubles [3P]).
+    m <= GABO_MVN_SAMPLE_MAX_M: one launch (gabo_mvn_sample), no host synchronisation; a matrix that no rung factors raises
+    RuntimeError("... not positive definite") through set_error_checking's machinery (at the call, or at the next check_deferred()).
+    Larger m: the same ladder around torch.linalg.cholesky_ex (one host wait per rung) and a matrix product; the normals are the same
+    stream either way (mvn_base_samples), so a seed gives the same draw on both paths.
+    z: base_samples (sample_shape + (m,)) when given, else the stream `seed` (None: a seed from numpy's global generator).
+    return_scale_tril: -> (samples, L m x m, rung) with rung a 0-d int32 device tensor indexing the ladder."""
+    lib = _lib.load()
+    if not torch.is_tensor(cov) or not cov.is_cuda or cov.dtype != torch.float64 or cov.dim() != 2 or cov.shape[0] != cov.shape[1]:
+        raise ValueError("mvn_sample: cov must be an m x m fp64 tensor on a HIP device")
+    dev, m = cov.device, cov.shape[-1]
+    if m < 1:
+        raise ValueError("mvn_sample: empty covariance")
+    shape = tuple(int(s) for s in sample_shape)
+    count = 1
+    for s in shape:
+        count *= s
+    mu = _prep(torch.as_tensor(mean), dev).reshape(-1).contiguous()
+    if mu.numel() != m:
+        raise ValueError(f"mvn_sample: mean has {mu.numel()} entries, cov is {m} x {m}")
+    cv = cov.contiguous()
+    z = None
+    if base_samples is not None:
+        z = _prep(torch.as_tensor(base_samples), dev)
+        if tuple(z.shape) != shape + (m,):
+            raise ValueError(f"mvn_sample: base_samples must be {shape + (m,)}, got {tuple(z.shape)}")
+        z = z.reshape(count, m).contiguous()
+    if m > _lib.GABO_MVN_SAMPLE_MAX_M:
+        if z is None:
+            z = mvn_base_samples(count, m, seed, device=dev)
+        eye = torch.eye(m, dtype=torch.float64, device=dev)
+        for rung, jitter in enumerate(_lib.GABO_MVN_JITTER_LADDER):
+            L, info = torch.linalg.cholesky_ex(cv if jitter == 0.0 else cv + jitter * eye)
+            if int(info.item()) == 0 and bool(torch.isfinite(L).all()):
+                break
+        else:
+            raise RuntimeError(_MVN_MESSAGE)
+        out = (mu + z @ L.transpose(-1, -2)).reshape(shape + (m,))
+        return (out, L, torch.tensor(rung, dtype=torch.int32, device=dev)) if return_scale_tril else out
+    out = torch.empty(count, m, dtype=torch.float64, device=dev)
+    tril = torch.empty(m, m, dtype=torch.float64, device=dev) if return_scale_tril else None
+    status = torch.zeros(2, dtype=torch.int32, device=dev)       # (a word of its own: status[1], the rung, outlives the error check)
+    with _on(dev):
+        _lib.check(lib.gabo_mvn_sample(mu.data_ptr(), cv.data_ptr(), m, count, _mvn_seed(seed) if z is None else 0,
+                                       None if z is None else z.data_ptr(), out.data_ptr(), None if tril is None else tril.data_ptr(),
+                                       status.data_ptr(), _stream_ptr(dev)), "gabo_mvn_sample")
+    _raise_if_not_spd(status, "gabo_mvn_sample", message=_MVN_MESSAGE)
+    out = out.reshape(shape + (m,))
+    return (out, tril, status[1]) if return_scale_tril else out
+
+
 def spd_acq_prepare_train(train_mandel):
     """Entry-major Cholesky factors of the training matrices for spd_acq_eval (d_vec x n)."""
     lib = _lib.load()

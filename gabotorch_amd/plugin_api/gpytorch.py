@@ -31,3 +31,11 @@ except Exception:                        # noqa: BLE001
     likelihoods = _types.SimpleNamespace(GaussianLikelihood=GaussianLikelihood,
                                          gaussian_likelihood=_types.SimpleNamespace(GaussianLikelihood=GaussianLikelihood))
     mlls = _types.SimpleNamespace(ExactMarginalLogLikelihood=ExactMarginalLogLikelihood)
+
+try:
+    from gpytorch import distributions  # noqa: F401
+except Exception:                        # noqa: BLE001
+    from .. import models as _models
+
+    # what `model(x_test)` returns in the reference's GP-regression demos (examples/kernels/spd/spd_kernels.py:168-174)
+    distributions = _types.SimpleNamespace(MultivariateNormal=_models.MultivariateNormal)

@@ -307,6 +307,43 @@ int gabo_gram_extreme_eig(const double* e, int64_t batch, int64_t n, const doubl
                           double* out, void* workspace, size_t workspace_bytes, gabo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Joint posterior of the exact GP over a test set, and samples from it: `preds = model(x_test)`, preds.mean / .variance /
+ * .covariance_matrix and preds.sample() of examples/kernels/spd/spd_kernels.py:168-174 and examples/kernels/sphere/sphere_kernels.py:147-150
+ * ([3P] gpytorch's exact prediction and MultivariateNormal).  fp64 throughout (csrc/gp_posterior.hip).
+ *
+ * gabo_gp_posterior_joint: with L L^T = Ky = outputscale k + noise I, linv = L^-1 (n x n row-major, only its lower triangle is read) and
+ * alpha = Ky^-1 (y - mean) - the prediction cache of gabo_gp_factor, or of any other factorisation -
+ *   kstar: m x n BASE kernel values k(x*_i, x_j);  cov: m x m, on entry the BASE Gram matrix k(x*_i, x*_j) of the test set (its lower
+ *   triangle and diagonal are read), on return Sigma = outputscale k** - V V^T with V = outputscale kstar linv^T, both triangles, exactly
+ *   symmetric;  mean_out[i] = mean + outputscale kstar[i] . alpha;  var_out = the diagonal of Sigma, the same bits.
+ * The latent f: no observation noise is added.  Two launches (projection, then 64 x 64 tiles i >= j of the covariance with their mirror
+ * images); every sum runs over the training points in ascending order, so an entry's bits do not depend on m.  A non-finite input makes
+ * the entries it touches non-finite; it is no error.
+ * workspace: V, padded: *_workspace_bytes(m, n) = ceil(m / 64) 64 * ceil(n / 16) 16 doubles (0 for arguments that are refused).
+ * GABO_ERR_DIM for n > GABO_GP_MLL_LARGE_MAX_N or m > GABO_GP_POSTERIOR_MAX_M; GABO_ERR_ARG for m < 1, n < 1, a null pointer or a workspace
+ * smaller than that - all before any HIP call. */
+#define GABO_GP_POSTERIOR_MAX_M 1048576
+size_t gabo_gp_posterior_joint_workspace_bytes(int64_t m, int64_t n);
+int gabo_gp_posterior_joint(const double* kstar, double* cov, const double* linv, const double* alpha, int64_t m, int64_t n, double mean,
+                            double outputscale, double* mean_out, double* var_out, void* workspace, size_t workspace_bytes,
+                            gabo_stream_t stream);
+
+/* samples x m draws out[s] = mean + L z_s from N(mean, cov) in ONE launch of one workgroup, m <= GABO_MVN_SAMPLE_MAX_M (GABO_ERR_DIM beyond:
+ * the packed lower triangle lives in LDS).  cov: m x m row-major, the lower triangle and the diagonal are read.  L L^T = cov + j I for the
+ * first j of the ladder 0, 1e-8, 1e-7, 1e-6 (absolute) that factors; a non-positive or NaN pivot restarts from the input with the next j.
+ * This is [3P] gpytorch's psd_safe_cholesky for doubles, restated from memory: PARITY UNPINNED.
+ *   status: int[2] ON THE DEVICE.  status[1] = the rung used (0 ... 3; 4 when none factors); status[0] = GABO_ERR_NOT_SPD when none
+ *   factors (out and scale_tril are then unspecified) and is left as it is otherwise.
+ *   z_s = base_samples[s] (samples x m) when given; otherwise standard normals of the library's Philox stream: key = seed, item = s, draw k
+ *   gives coordinates 2k and 2k + 1 by Box-Muller, fourth counter word 0x6d766e7a - gabo_mvn_base_samples writes exactly these.
+ *   scale_tril: NULL, or m x m for L (zeros above the diagonal).
+ * GABO_ERR_ARG for m < 1, samples < 0 or a null mean / cov / status / out (out may be NULL with samples == 0). */
+#define GABO_MVN_SAMPLE_MAX_M 192
+int gabo_mvn_sample(const double* mean, const double* cov, int64_t m, int64_t samples, uint64_t seed, const double* base_samples,
+                    double* out, double* scale_tril, int* status, gabo_stream_t stream);
+int gabo_mvn_base_samples(double* out, int64_t samples, int64_t m, uint64_t seed, gabo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * One evaluation of the surrogate-fit objective of HD-GaBO with its gradient, as one HOST call (it returns with the numbers):
  * the marginal log likelihood of ScaleKernel(NestedSpdLogEuclideanGaussianKernel) at a projection matrix W and scalar hyper-parameters.
  * Replaces the closure fit_gpytorch_manifold differentiates by autograd   manifold_optimization/manifold_gp_fit.py:54-222
