@@ -20,6 +20,17 @@ namespace gabo {
 // fixed form a dimension uses, if any: spd_pair_gauss_only_orientation (spd_pairwise_body.hpp).
 enum QlOrient : int { kQlOrientPerLane = 0, kQlOrientCol0 = 1, kQlOrientLast = 2 };
 
+// Cheaper forms of the per-sweep control of tridiag_eigenvalues (a bit mask; which a dimension uses: spd_pair_gauss_only_sweepctl,
+// spd_pairwise_body.hpp).  Each replaces a value that only feeds the shift or a threshold compare by one that is cheaper to form; none touches
+// the arithmetic of a sweep step.  Only for the fixed orientations: the strict path keeps the plain control and its pinned bits.
+//   kQlCtlDenormalZero     a deflated e2[l] is cleared in its HIGH word only, in place (one v_cndmask_b32 instead of two): what is left is a
+//                          denormal <= 4.3e-314 where the plain form has an exact 0 (fp64 denormals are not flushed: the kernels run in denorm mode 3)
+//   kQlCtlHwSqrt           the shift's square root is the bare v_sqrt_f64 (2^-23) instead of x * v_rsq_f64(x): one instruction less, and sqrt(0) = 0
+//   kQlCtlStageThreshold   the idle test of block l + 1 compares e2[l+1] with the threshold of stage l, eps2 |d_l d_{l+1}|, already formed for
+//                          e2[l], instead of its own eps2 |d_{l+1} d_{l+2}|: two multiplies less.  It decides only whether a look-ahead lane
+//                          spends the sweep on block l + 1 or sits it out; stage l + 1 deflates by its own threshold as before.
+enum QlSweepCtl : int { kQlCtlPlain = 0, kQlCtlDenormalZero = 1, kQlCtlHwSqrt = 2, kQlCtlStageThreshold = 4 };
+
 // m: packed lower triangle of a symmetric D x D matrix (destroyed).  Out: dg[0..D-1] diagonal and
 // e2[0..D-2] squared off-diagonals of the similar tridiagonal matrix (e2[D-1] = 0).
 template <int D, int ORIENT = kQlOrientPerLane>
@@ -116,8 +127,10 @@ __device__ __forceinline__ double mul_floor_p(double a, double b) {
 // only divergence is the iteration count per stage.  An interior off-diagonal that is (or becomes) negligible is
 // simply swept through: the recurrence restarts by itself there (c -> 1, s -> 0).  p > 0 is an invariant (see
 // `mul_floor_p`), hence r = p + bb > 0 and c = p / r > 0: no division can see a zero.  The last 2x2 block is closed form.
-template <int D, int ORIENT = kQlOrientPerLane>
+template <int D, int ORIENT = kQlOrientPerLane, int CTL = kQlCtlPlain>
 __device__ __forceinline__ void tridiag_eigenvalues(double (&dg)[D], double (&e2)[D], const double eps2_arg = 0.0) {
+    static_assert(CTL == kQlCtlPlain || ORIENT != kQlOrientPerLane, "the strict path keeps the plain sweep control");
+    constexpr bool kDenormalZero = (CTL & kQlCtlDenormalZero) != 0, kHwSqrt = (CTL & kQlCtlHwSqrt) != 0, kStageThreshold = (CTL & kQlCtlStageThreshold) != 0;
     // Deflation threshold on e2[l] / |d[l] d[l+1]|.  LAPACK uses eps^2 (4.9e-32); 1e-20 is enough here: dropping an
     // off-diagonal e perturbs a SYMMETRIC function of the eigenvalues (sum log^2) only to second order, ~e^2 f'' <= 1e-20,
     // whatever the gap, and the iteration converges cubically, so the looser test saves the last sweep of many stages
@@ -168,16 +181,26 @@ __device__ __forceinline__ void tridiag_eigenvalues(double (&dg)[D], double (&e2
             // through as the identity (bb = 0 => c = 1, s = 0) whatever p has become; with a merely negligible e2[l] a tiny p at
             // the end of a converged sweep makes s = bb / (p + bb) large and the pass-through re-couples the deflated row
             // (tools/sim/ql_lookahead_sim.py: 180 -> 189 steps without the zeroing, 180 -> 129 with it).
-            const bool done0 = e2[l] <= eps2 * __builtin_fabs(dg[l] * dg[l + 1]);
+            constexpr bool kAhead = l + 1 <= D - 3;           // stage l has a block l + 1 to look ahead to
+            const double thr0 = eps2 * __builtin_fabs(dg[l] * dg[l + 1]);
+            const bool done0 = e2[l] <= thr0;
             // the WAVE leaves stage l when its last lane has deflated e2[l] (a per-lane `break` would keep the wave here until every lane
             // had finished its look-ahead work too, at stage l's longer sweep extent).  Every active lane done: the mask of `done0` against the
             // mask of the active lanes - one vector compare (`ballot(!done0)` costs a second, NaN-aware one).
             if (__builtin_amdgcn_ballot_w64(done0) == __builtin_amdgcn_ballot_w64(true)) break;
-            const double e2l = done0 ? 0.0 : e2[l];        // (e2[l] itself is rewritten at the end of the sweep: s p = 0 for these lanes)
+            double e2l;
+            if constexpr (kDenormalZero && kAhead) {
+                // the high word alone, in place: the denormal that is left makes s = bb / (p + bb) <= 4.3e-314 / 1e-150 (p is floored, mul_floor_p),
+                // the identity as far as any double of the sweep can tell, and a lane that sits the sweep out passes the test again with it
+                e2[l] = __hiloint2double(done0 ? 0 : __double2hiint(e2[l]), __double2loint(e2[l]));
+                e2l = e2[l];
+            } else {
+                e2l = done0 ? 0.0 : e2[l];                   // (e2[l] itself is rewritten at the end of the sweep: s p = 0 for these lanes)
+            }
             double sa = dg[l], sb = dg[l + 1], se = e2l;
             bool idle = false;
-            if constexpr (l + 1 <= D - 3) {
-                const bool done1 = e2[l + 1] <= eps2 * __builtin_fabs(dg[l + 1] * dg[l + 2]);
+            if constexpr (kAhead) {
+                const bool done1 = e2[l + 1] <= (kStageThreshold ? thr0 : eps2 * __builtin_fabs(dg[l + 1] * dg[l + 2]));
                 idle = done0 && done1;                      // nothing to do within the look-ahead window: sit this sweep out
                 sa = done0 ? dg[l + 1] : sa;
                 sb = done0 ? dg[l + 2] : sb;
@@ -193,7 +216,10 @@ __device__ __forceinline__ void tridiag_eigenvalues(double (&dg)[D], double (&e2
                 // evaluated division-free as d_l - sign(delta) (sqrt(delta^2 + e2_l) - |delta|).  The cancellation of the
                 // rationalised form only costs ~eps |delta| in the SHIFT, which changes the convergence rate, never the result.
                 double delta = 0.5 * (sb - sa);
-                double root = sqrt_shift(__builtin_fma(delta, delta, se));
+                const double root2 = __builtin_fma(delta, delta, se);
+                double root;
+                if constexpr (kHwSqrt) root = __builtin_amdgcn_sqrt(root2);
+                else root = sqrt_shift(root2);
                 double sigma = sa - copysign_d(root - __builtin_fabs(delta), delta);
                 double gamma = dg[D - 1] - sigma;
                 double p = mul_floor_p(gamma, gamma);

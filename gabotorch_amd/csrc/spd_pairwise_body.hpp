@@ -40,7 +40,7 @@ struct SpdGcolPointer {
     __device__ __forceinline__ double operator[](int k) const { return p[(int64_t)k * stride]; }
 };
 
-template <int D, int ORIENT = kQlOrientPerLane, class GCOL>
+template <int D, int ORIENT = kQlOrientPerLane, int CTL = kQlCtlPlain, class GCOL>
 __device__ __forceinline__ double ai_sumsq(const double* __restrict__ W, const GCOL& Gj, const double* __restrict__ ltab, const double eps2 = 0.0) {
     constexpr int T = tri_size(D);
     // Column `col` of C = W G depends only on column `col` of G:  C[r][col] = sum_{k=col..r} W[r][k] G[k][col].
@@ -76,7 +76,7 @@ __device__ __forceinline__ double ai_sumsq(const double* __restrict__ W, const G
     });
     double dg[D], e2[D];
     tridiagonalize<D, ORIENT>(m, dg, e2);
-    tridiag_eigenvalues<D, ORIENT>(dg, e2, eps2);
+    tridiag_eigenvalues<D, ORIENT, CTL>(dg, e2, eps2);
     double s = 0.0;
     const LogTabRegs lr = LogTabRegs::load();
     static_for<D>([&](auto kk) { double lg = log_tab(dg[decltype(kk)::value], lr, ltab); s = __builtin_fma(lg, lg, s); });
@@ -158,6 +158,23 @@ constexpr bool spd_pair_gauss_only_instantiated(int d) { return d > 2 && d != 12
 constexpr int spd_pair_gauss_only_orientation(int d) { return d == 14 ? kQlOrientCol0 : kQlOrientLast; }
 #else
 constexpr int spd_pair_gauss_only_orientation(int d) { return GABO_PAIR_ORIENT; }      // (A/B builds: one form for every dimension)
+#endif
+// Sweep control of the eigenvalue iteration in the Gaussian-only instantiation (QlSweepCtl, spd_eig.hpp): all three cheaper forms, 25 -> 21 VALU per
+// sweep in the d = 10 listing (profiles/sweepctl_isa_count.txt), same registers, no spill.  Wave-level simulation (tools/sim/ql_orientation_sim.py
+// --sweepctl, profiles/sweepctl_sim.txt): d = 10, 111.3 -> 111.7 sweep steps and 17.34 -> 17.42 sweeps per wave-row - the idle test by stage l's
+// threshold idles a few lanes a sweep early - for QL VALU 2215 -> 2152; no stage beyond 7 sweeps, worst error of sum log^2 against LAPACK 1.2e-12 -> 1.4e-12.
+// Measured, N = 4096 Gram, parent / this form, two alternations per job (profiles/sweepctl_ab_elsewhere.txt): d = 3 0.239 / 0.239 -> 0.242 / 0.237 ms,
+// d = 4 0.398 -> 0.391, d = 5 0.586 / 0.592 -> 0.583 / 0.586, d = 6 0.789 -> 0.773, d = 7 1.025 -> 1.015, d = 8 1.356 -> 1.340, d = 9 1.676 -> 1.657,
+// d = 10 2.156 / 2.166 -> 2.140 / 2.145, d = 11 2.569 -> 2.547, d = 13 3.967 -> 3.934, d = 14 5.200 -> 5.166, d = 15 7.005 -> 6.931, d = 16 9.183 -> 9.029,
+// d = 17 9.930 / 9.945 -> 9.917 / 9.955 (inside the spread), d = 18 12.18 -> 11.95, d = 19 14.91 -> 14.86.  d = 20 keeps the plain control: 20.906 / 20.924 -> 20.955 /
+// 20.969 and, in a second job, 20.917 / 20.963 -> 20.950 / 20.986 - 0.15 % slower four times out of four.
+// Not in the tree, with their numbers in CHANGELOG: the look-ahead operands selected by their high words alone (the compiler pays for every saved
+// select with a move), one multiply shared by the two deflation tests (subsumed by the stage threshold), no idle test at all (fastest, but the
+// neighbours of a lane that never converges then sweep 60 times per stage and lose a digit).
+#ifndef GABO_PAIR_SWEEPCTL
+constexpr int spd_pair_gauss_only_sweepctl(int d) { return d == 20 ? kQlCtlPlain : (kQlCtlDenormalZero | kQlCtlHwSqrt | kQlCtlStageThreshold); }
+#else
+constexpr int spd_pair_gauss_only_sweepctl(int d) { return GABO_PAIR_SWEEPCTL; }      // (A/B builds: one form for every dimension)
 #endif
 template <int D, bool GAUSS_ONLY, bool BUFFER_ONLY>
 __global__ __launch_bounds__(256, (D > GABO_PAIR_TWO_WAVE_MAX_DIM ? 1 : GABO_PAIR_WAVES)) void spd_ai_pairwise_kernel(const double* __restrict__ Winv, const double* __restrict__ G,
@@ -267,7 +284,7 @@ __global__ __launch_bounds__(256, (D > GABO_PAIR_TWO_WAVE_MAX_DIM ? 1 : GABO_PAI
             SpdGcolBuffer gb = gbuf;
             asm volatile("" : "+v"(gb.voff));                  // the 55 G loads stay inside the row loop (see the general loop below)
             asm volatile("" : "+s"(gb.stride_bytes));
-            const double s = ai_sumsq<D, spd_pair_gauss_only_orientation(D)>(W, gb, ltab, eps2);
+            const double s = ai_sumsq<D, spd_pair_gauss_only_orientation(D), spd_pair_gauss_only_sweepctl(D)>(W, gb, ltab, eps2);
             double val;
             if constexpr (kTabExp) {
                 val = exp_neg_tab(-((s + 1e-15) * beta), ec, ec3, tab);

@@ -21,6 +21,23 @@ column as the kernel's clamped lanes do).  Per case: steps and sweeps per wave, 
 LARGEST sweep count of any stage of any wave (the kernel caps a stage at 60) and the worst absolute error of sum log^2 lambda against LAPACK.
 
     python tools/sim/ql_orientation_sim.py [D ...] > profiles/orient_sim.txt
+
+--sweepctl: the kept orientation of every dimension (spd_pair_gauss_only_orientation) with cheaper forms of the QL's per-sweep control, the
+candidates of CHANGELOG "sweep control of the Gaussian-only QL iteration", alone and together:
+
+    c1    look-ahead lanes take only the HIGH words of their shift operands (d[l+1], d[l+2], e2[l+1]) from block l+1, the low words from block l:
+          the block-(l+1) values to 2^-20 relative
+    c2    one product eps2 d[l+1] shared by the deflation tests of e2[l] and e2[l+1] (another rounding order of the same thresholds)
+    c3    a deflated e2[l] keeps its low word: a denormal below 4.3e-314 instead of an exact 0                              (kQlCtlDenormalZero)
+    far   look-ahead lanes shift by the root of block l+1 next to d[l+2] instead of the one next to d[l+1] (sa = d[l+2], sb = d[l+1]: one select less)
+    sq    the shift's root from the bare v_sqrt_f64: modelled as a relative perturbation of the root, uniform in +-2^-23     (kQlCtlHwSqrt)
+    nod1  no idle test: a lane that has deflated e2[l] always sweeps on block l+1, converged or not
+    c2b   the idle test of block l+1 against the threshold of stage l, eps2 |d[l] d[l+1]|, instead of its own                (kQlCtlStageThreshold)
+
+per case steps and sweeps per wave-row, the QL's VALU per wave-row at 16 per step + the form's per-sweep count (SWEEP_VALU, from the listing),
+the largest sweep count of a stage and the worst error of sum log^2 lambda against LAPACK.
+
+    python tools/sim/ql_orientation_sim.py --sweepctl [D ...] > profiles/sweepctl_sim.txt
 """
 import os
 import sys
@@ -38,11 +55,22 @@ ORIENTATIONS = ("col0/rule", "col0/first", "col0/last", "last/rule", "last/last"
 FAMILIES = ("bench", "near", "ratio1e6")
 BENCH_ROWS = (5, 100, 2000, 3000)
 N1, N2 = 40, 300
+# --sweepctl: the forms simulated and the VALU instructions of sweep control per sweep that the gfx950 listing of each has (d = 10,
+# profiles/sweepctl_isa_count.txt; "far" and "c2b" alone were not built: 25 less the two v_cndmask_b32 of one select of a double, 25 less two multiplies)
+SWEEP_FORMS = ((), ("c1",), ("c2",), ("c3",), ("c2", "c3"), ("c1", "c2", "c3"), ("far",), ("sq",), ("sq", "nod1"), ("c2", "c3", "sq"), ("c2", "c3", "sq", "nod1"), ("c2b",), ("c2b", "c3"), ("c2b", "c3", "sq"))
+SWEEP_VALU = {(): 25, ("c1",): 25, ("c2",): 24, ("c3",): 24, ("c2", "c3"): 23, ("c1", "c2", "c3"): 57, ("far",): 23, ("sq",): 24, ("sq", "nod1"): 21,
+              ("c2", "c3", "sq"): 22, ("c2", "c3", "sq", "nod1"): 20, ("c2b",): 23, ("c2b", "c3"): 22, ("c2b", "c3", "sq"): 21}
+_HI = np.int64(-1) << np.int64(32)
 
 
-def ql(dg, e2, rule):
+def _words(hi, lo):
+    """the double with the high word of `hi` and the low word of `lo`"""
+    return ((hi.view(np.int64) & _HI) | (lo.view(np.int64) & ~_HI)).view(np.float64)
+
+
+def ql(dg, e2, rule, ctl=()):
     """Wave-level model of tridiag_eigenvalues (look-ahead window 1, deflated e2[l] zeroed, p floored, f^2 t form).  rule: apply the per-lane
-    reversal first.  Returns (eigenvalues, sweep steps, sweeps, largest sweep count of a stage of a wave)."""
+    reversal first; ctl: forms of sweep control (module docstring, --sweepctl).  Returns (eigenvalues, sweep steps, sweeps, largest sweep count of a stage of a wave)."""
     dg, e2 = dg.copy(), e2.copy()
     n, D = dg.shape
     assert n % WAVE == 0
@@ -59,7 +87,16 @@ def ql(dg, e2, rule):
     for l in range(D - 2):
         per_wave = np.zeros(n // WAVE, dtype=int)
         for it in range(CAP):
-            c_l = conv(l)
+            if "c2" in ctl and l + 1 <= D - 3:
+                x = EPS2 * dg[:, l + 1]
+                c_l = e2[:, l] <= np.abs(x * dg[:, l])
+                c_l1 = e2[:, l + 1] <= np.abs(x * dg[:, l + 2])
+            elif "c2b" in ctl and l + 1 <= D - 3:
+                thr = EPS2 * np.abs(dg[:, l] * dg[:, l + 1])
+                c_l, c_l1 = e2[:, l] <= thr, e2[:, l + 1] <= thr
+            else:
+                c_l = conv(l)
+                c_l1 = conv(l + 1) if l + 1 <= D - 3 else None
             wave_active = (~c_l).reshape(-1, WAVE).any(1)
             if not wave_active.any():
                 break
@@ -67,19 +104,31 @@ def ql(dg, e2, rule):
             steps += int(wave_active.sum()) * (D - 1 - l)
             sweeps += int(wave_active.sum())
             in_active = np.repeat(wave_active, WAVE)
-            e2l = np.where(c_l, 0.0, e2[:, l])
+            if "c3" in ctl:
+                # (in place, as the kernel does it: a lane that sits the sweep out keeps the denormal)
+                e2[c_l & in_active, l] = _words(np.zeros(n), e2[:, l])[c_l & in_active]
+                e2l = e2[:, l].copy()
+            else:
+                e2l = np.where(c_l, 0.0, e2[:, l])
             k = np.full(n, l)
             work = ~c_l
             if l + 1 <= D - 3:
-                ahead = c_l & in_active & ~conv(l + 1)
+                ahead = c_l & in_active if "nod1" in ctl else c_l & in_active & ~c_l1
                 k[ahead] = l + 1
                 work = work | ahead
             idx = lanes[work]
             kx = k[idx]
             d0, d1 = dg[idx, kx], dg[idx, kx + 1]
             ee = np.where(kx == l, e2l[idx], e2[idx, kx])
+            if "c1" in ctl and l + 1 <= D - 3:
+                d0, d1, ee = _words(d0, dg[idx, l]), _words(d1, dg[idx, l + 1]), _words(ee, e2l[idx])
+            if "far" in ctl and l + 1 <= D - 3:
+                la = kx == l + 1
+                d0, d1 = np.where(la, dg[idx, l + 2], d0), np.where(la, dg[idx, l + 1], d1)
             delta = 0.5 * (d1 - d0)
             root = np.sqrt(delta * delta + ee)
+            if "sq" in ctl:
+                root = root * (1.0 + 2.0 ** -23 * np.random.default_rng(1000 * l + it).uniform(-1.0, 1.0, len(idx)))
             sigma = d0 - np.copysign(root - np.abs(delta), delta)
             gamma = dg[idx, D - 1] - sigma
             p = gamma * gamma + 1e-150
@@ -188,7 +237,60 @@ def run(d, name):
     return {o: (t[0] / nw, t[1] / nw, 16 * t[0] / nw + 25 * t[1] / nw, t[2], t[3]) for o, t in tot.items()}
 
 
+def kept_orientation(d):
+    """spd_pair_gauss_only_orientation (csrc/spd_pairwise_body.hpp)"""
+    return "col0/last" if d == 14 else "last/last"
+
+
+def run_sweepctl(d, name):
+    """{form: (steps, sweeps, QL VALU, largest stage, err)} per wave-row of the kept orientation of dimension d"""
+    x1, x2 = family(d, name)
+    pad = (-x2.shape[0]) % WAVE
+    if pad:
+        x2 = np.concatenate([x2, np.repeat(x2[-1:], pad, 0)], 0)
+    Linv = np.linalg.inv(np.linalg.cholesky(x1))
+    tot = {f: [0, 0, 0, 0.0] for f in SWEEP_FORMS}
+    for i in range(x1.shape[0]):
+        M = np.einsum("ab,nbc,dc->nad", Linv[i], x2, Linv[i])
+        M = 0.5 * (M + M.transpose(0, 2, 1))
+        ref = np.sum(np.log(np.linalg.eigvalsh(M)) ** 2, 1)
+        dg, e2, rule = oriented(M, kept_orientation(d))
+        for f in SWEEP_FORMS:
+            ev, steps, sweeps, worst = ql(dg, e2, rule, f)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                err = np.abs(np.sum(np.log(ev) ** 2, 1) - ref)
+            t = tot[f]
+            t[0] += steps
+            t[1] += sweeps
+            t[2] = max(t[2], worst)
+            t[3] = max(t[3], float(np.max(err / np.maximum(1.0, ref))) if name == "ratio1e6" else float(np.max(err)))
+    nw = x1.shape[0] * x2.shape[0] // WAVE
+    return {f: (t[0] / nw, t[1] / nw, 16 * t[0] / nw + SWEEP_VALU[f] * t[1] / nw, t[2], t[3]) for f, t in tot.items()}
+
+
+def main_sweepctl(dims):
+    print("# sweep control of the Gaussian-only QL (tools/sim/ql_orientation_sim.py --sweepctl): the kept orientation per dimension, eps2 1e-14, wave = 64 columns")
+    print("# forms: see the module docstring;  QL VALU = 16 steps + (per-sweep count of the form: " +
+          ", ".join(f"{'+'.join(f) or 'today'} {SWEEP_VALU[f]}" for f in SWEEP_FORMS) + ") sweeps")
+    print("# err = worst |sum log^2 lambda - LAPACK's| (ratio1e6: relative to max(1, sum log^2))")
+    summary = {}
+    for d in dims:
+        for name in FAMILIES:
+            res = run_sweepctl(d, name)
+            print(f"d = {d:2d}  {name}  ({kept_orientation(d)})")
+            for f in SWEEP_FORMS:
+                st, sw, valu, worst, err = res[f]
+                print(f"    {'+'.join(f) or 'today':9s} steps {st:7.1f}  sweeps {sw:6.2f}  QL VALU {valu:7.0f}  max stage {worst:2d}  err {err:.1e}", flush=True)
+            if name == "bench":
+                summary[d] = res
+    print("# summary, benchmark family: QL VALU per wave-row, today -> each form (ratio)")
+    for d, res in summary.items():
+        print(f"d = {d:2d}: {res[()][2]:6.0f}" + "".join(f"  {'+'.join(f)} {res[f][2]:6.0f} ({res[f][2] / res[()][2]:.4f})" for f in SWEEP_FORMS[1:]))
+
+
 def main():
+    if "--sweepctl" in sys.argv[1:]:
+        return main_sweepctl(tuple(int(a) for a in sys.argv[1:] if a != "--sweepctl") or DIMS)
     dims = tuple(int(a) for a in sys.argv[1:]) or DIMS
     print("# QL orientation study (tools/sim/ql_orientation_sim.py): eps2 1e-14, look-ahead window 1, floor on p, f^2 t form, wave = 64 columns")
     print("# steps, sweeps: per wave-row;  QL VALU = 16 steps + 25 sweeps;  max stage = largest sweep count of one stage of one wave (cap 60)")
