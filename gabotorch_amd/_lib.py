@@ -26,6 +26,7 @@ GABO_GRAM_EIG_MAX_N = 1024
 GABO_GRAM_EIG_LDS_MAX_N = 192          # up to here the triangle of gabo_gram_extreme_eig lives in LDS and the call needs no workspace
 GABO_GP_POSTERIOR_MAX_M = 1048576
 GABO_MVN_SAMPLE_MAX_M = 192            # up to here gabo_mvn_sample factors the covariance in LDS, one launch
+GABO_GP_CONDITION_MAX_T = 16           # new points per gabo_gp_condition call
 GABO_MVN_JITTER_LADDER = (0.0, 1e-8, 1e-7, 1e-6)      # status[1] of gabo_mvn_sample indexes it
 GABO_METRIC_AFFINE_INVARIANT, GABO_METRIC_LOG_EUCLIDEAN, GABO_METRIC_FROBENIUS = 0, 8, 16
 GABO_CONSTRAINT_MAX_EIGENVALUE, GABO_CONSTRAINT_MIN_EIGENVALUE = 0, 1
@@ -129,6 +130,8 @@ SIGNATURES = {
     "gabo_gp_posterior_joint": (_I, [_P, _P, _P, _P, _I64, _I64, _D, _D, _P, _P, _P, _SZ, _P]),
     "gabo_mvn_sample": (_I, [_P, _P, _I64, _I64, _c.c_uint64, _P, _P, _P, _P, _P]),
     "gabo_mvn_base_samples": (_I, [_P, _I64, _I64, _c.c_uint64, _P]),
+    "gabo_gp_condition_workspace_bytes": (_SZ, [_I64, _I64]),
+    "gabo_gp_condition": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _D, _D, _D, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "gabo_spd_acq_max_train": (_I64, [_I]),
     "gabo_spd_acq_prepare_train": (_I, [_P, _P, _I64, _I, _P, _P]),
     "gabo_spd_acq_eval": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I, _D, _I, _D, _D, _D, _D, _I, _I, _D, _P, _P, _P]),

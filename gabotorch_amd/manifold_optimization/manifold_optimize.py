@@ -109,6 +109,37 @@ def joint_optimize_manifold(acq_function, manifold, solver, q, num_restarts, raw
     return best
 
 
+def sequential_optimize_manifold(acq_function, manifold, solver, q, num_restarts, raw_samples, bounds, sample_type=torch.float64,
+                                 options=None, inequality_constraints=None, equality_constraints=None, pre_processing_manifold=None,
+                                 post_processing_manifold=None, approx_hessian=False, solver_init_conds=False):
+    """A batch of q proposals, `q x d` in the order chosen, by greedy "Kriging believer" selection (Ginsbourger et al. 2010; not in the
+    reference, whose analytic acquisitions ignore q): row 0 is joint_optimize_manifold's candidate; row k is the same sweep on
+    ExpectedImprovement over the model conditioned on rows 0 ... k - 1 with the believer's targets (the posterior mean at each of them:
+    models.*.condition_on_observations - bordered updates of the prediction cache on the device, no new factorisation), best_f and maximize
+    unchanged.  Every sweep is a joint_optimize_manifold call with the arguments given here, so it takes whatever plan that function picks.
+    acq_function: models.ExpectedImprovement over models.ExactGP or models.SingleTaskGP; the rows are the model's input vectors."""
+    from .. import models
+    if isinstance(acq_function, models.PosteriorMean):
+        raise ValueError("sequential_optimize_manifold: the believer's observation does not change the posterior mean, so every row would be the "
+                         "same point; use ExpectedImprovement")
+    if type(acq_function) is not models.ExpectedImprovement or type(getattr(acq_function, "model", None)) not in (models.ExactGP, models.SingleTaskGP):
+        raise NotImplementedError("sequential_optimize_manifold supports models.ExpectedImprovement over models.ExactGP or models.SingleTaskGP, got "
+                                  f"{type(acq_function).__name__} over {type(getattr(acq_function, 'model', None)).__name__}")
+    q = int(q)
+    if q < 1:
+        raise ValueError(f"sequential_optimize_manifold: q = {q}")
+    acq, rows = acq_function, []
+    for k in range(q):
+        rows.append(joint_optimize_manifold(acq, manifold, solver, 1, num_restarts, raw_samples, bounds, sample_type=sample_type, options=options,
+                                            inequality_constraints=inequality_constraints, equality_constraints=equality_constraints,
+                                            pre_processing_manifold=pre_processing_manifold, post_processing_manifold=post_processing_manifold,
+                                            approx_hessian=approx_hessian, solver_init_conds=solver_init_conds))
+        if k + 1 < q:
+            x = rows[-1].detach().reshape(1, -1).to(acq.model.train_x.device, torch.float64)
+            acq = models.ExpectedImprovement(acq.model.condition_on_observations(x), best_f=acq_function.best_f, maximize=acq_function.maximize)
+    return rows[0] if q == 1 else torch.cat([r.reshape(1, -1) for r in rows])
+
+
 def _library_constraint(con):
     """functools.partial over one of the library's eigenvalue constraints (plain or stated in the original space of a nested
     SPD mapping) or sphere constraints (coordinate bounds, geodesic ball): torch code without host synchronisation, safe to capture

@@ -108,6 +108,72 @@ def _joint_posterior(base_kernel, outputscale, train_x, linv, alpha, mean, X):
         return MultivariateNormal(_ops._out(mu, out_dev), _ops._out(cov, out_dev), _ops._out(var, out_dev))
 
 
+def _drop_caches(model):
+    model._cache = None
+    model._cache_linv_t = None
+    model._cache_factors = None
+    model._cache_kinv = None
+
+
+def _held(model, name):
+    """what `model` keeps under `name` for exactly its current cache object (None otherwise)"""
+    held = getattr(model, name, None)
+    return held[1] if held is not None and model._cache is not None and held[0] is model._cache else None
+
+
+def _condition_cache(model, base_kernel, outputscale, noise, mean, X, Y, holder):
+    """The caches of `model` (filled) extended by the points X (t x d_vec) with targets Y (t, or None: the believer's) through
+    ops.gp_condition -> (train_x, train_y, linv, linv_t, alpha, kinv or None, factors or None) of the n + t points.  The two kernel strips,
+    old x new and new x new, are ONE launch of the kernel's own, forward([train_x; X], X) ((n + t) x t), read with the EARLIER point as
+    first argument: the orientation in which the x1-is-x2 build of a training Gram matrix evaluates its entries (i <= j, then mirrored) -
+    the library's SPD kernels factor their first argument, so k(a, b) and k(b, a) differ in the last bits, and those bits times cond(Ky)
+    would separate this cache from a fresh model's.  The two arguments are different tensors, so the launch never takes the x1-is-x2
+    route: the entry of point b against an earlier point a is the same arithmetic whether a arrived in this call or in an earlier one,
+    and chained calls give the bits of one call.  holder: the models whose caches a failed update drops (the caller appends the model
+    it builds)."""
+    if not torch.is_tensor(X) or X.dim() != 2 or X.shape[0] < 1:
+        raise ValueError(f"condition_on_observations: X must be one set of new points, t x d_vec, got {tuple(getattr(X, 'shape', ()))}")
+    train_x, train_y = model.train_x, model.train_y
+    if train_x.dim() != 2 or not train_x.is_cuda:
+        raise ValueError("condition_on_observations: the model's training set must be one n x d_vec set on a HIP device")
+    if X.device != train_x.device or X.shape[-1] != train_x.shape[-1]:
+        raise ValueError(f"condition_on_observations: X {tuple(X.shape)} on {X.device} does not extend the training set {tuple(train_x.shape)} on "
+                         f"{train_x.device}")
+    t = X.shape[0]
+    if Y is not None:
+        Y = torch.as_tensor(Y).to(train_x.device, torch.float64).reshape(-1)
+        if Y.numel() != t:
+            raise ValueError(f"condition_on_observations: {Y.numel()} targets for {t} points")
+    linv, alpha = model._cache[0], model._cache[1]
+    kinv, factors = _held(model, "_cache_kinv"), _held(model, "_cache_factors")
+    with torch.no_grad():
+        X = X.double().contiguous()
+        n = train_x.shape[0]
+        all_x = torch.cat([train_x, X])
+        strip = base_kernel.forward(all_x, X).double()
+        if tuple(strip.shape) != (n + t, t):
+            raise ValueError("condition_on_observations: the kernel returned a batch of matrices; one set of new points at a time")
+        kcross, knew = strip[:n].t().contiguous(), strip[n:].t().contiguous()
+
+        def drop():
+            for m in holder:
+                _drop_caches(m)
+        linv_n, linv_t_n, alpha_n, kinv_n, y_used = _ops.gp_condition(linv, alpha, kcross, knew, Y, outputscale=float(outputscale), noise=float(noise),
+                                                                      mean=float(mean), kinv=kinv, want_linv_t=True, on_fail=drop)
+        if factors is not None:
+            factors = torch.cat([factors, _ops.spd_acq_prepare_train(X)], dim=1)
+        return (all_x, torch.cat([train_y.to(train_x.device), y_used]), linv_n, linv_t_n, alpha_n, kinv_n, factors)
+
+
+def _install_caches(model, cache, linv_t, kinv, factors):
+    """tied to the cache object by identity, exactly as the models' own routes tie them"""
+    model._cache = cache
+    model._cache_linv_t = (cache, linv_t)
+    model._cache_kinv = (cache, kinv)
+    if factors is not None:
+        model._cache_factors = (cache, factors)
+
+
 class ExactGP(torch.nn.Module):
     def __init__(self, train_x, train_y, base_kernel, outputscale=1.0, noise=1e-2, mean=None):
         super().__init__()
@@ -190,6 +256,20 @@ class ExactGP(torch.nn.Module):
         Linv, alpha = self._train_cache()
         _ops.check_deferred()
         return _joint_posterior(self.base_kernel, self.outputscale, self.train_x, Linv, alpha, self.mean, X)
+
+    def condition_on_observations(self, X, Y=None):
+        """gpytorch's ExactGP.condition_on_observations / get_fantasy_model [3P] for prediction: a NEW model over the training set extended
+        by X (t x d_vec, on the model's device) with targets Y (t), or - Y=None - the "Kriging believer" targets, the posterior mean at
+        each new point given everything before it.  Its caches come from bordered O(n^2) updates of this model's (ops.gp_condition: no
+        new factorisation, no host synchronisation); this model and its caches are untouched.  The kernel is shared, outputscale, noise
+        and mean are kept (the mean is not re-estimated).  Chained calls give the bits of one call with the points stacked."""
+        self._train_cache()
+        holder = []
+        tx, ty, linv, linv_t, alpha, kinv, factors = _condition_cache(self, self.base_kernel, self.outputscale, self.noise, self.mean, X, Y, holder)
+        new = ExactGP(tx, ty, self.base_kernel, outputscale=self.outputscale, noise=self.noise, mean=self.mean)
+        _install_caches(new, (linv, alpha), linv_t, kinv, factors)
+        holder.append(new)
+        return new
 
 
 class ExpectedImprovement(torch.nn.Module):
@@ -635,12 +715,30 @@ class SingleTaskGP(torch.nn.Module):
         Linv, alpha, mu = self._ensure_cache()
         from . import ops as _ops
         _ops.check_deferred()
+        base, outputscale = self._base_and_outputscale()
+        return _joint_posterior(base, outputscale, self.train_x, Linv, alpha, float(mu), X)
+
+    def _base_and_outputscale(self):
         cm = self.covar_module
         if hasattr(cm, "base_kernel") and type(cm).__name__ == "ScaleKernel" and cm.raw_outputscale.numel() == 1:
-            base, outputscale = cm.base_kernel, float(cm.outputscale.detach())
-        else:
-            base, outputscale = cm, 1.0
-        return _joint_posterior(base, outputscale, self.train_x, Linv, alpha, float(mu), X)
+            return cm.base_kernel, float(cm.outputscale.detach())
+        return cm, 1.0
+
+    def condition_on_observations(self, X, Y=None):
+        """As ExactGP.condition_on_observations: a new SingleTaskGP for prediction over the training set extended by X (t x d_vec) with
+        targets Y, or the believer's (Y=None); the covariance module, the noise and the mean constant are the same objects, frozen at their
+        current values as posterior() freezes them.  The kernel strips come from the covariance module's own launches: any kernel of the
+        library, nested ones included."""
+        _, _, mu = self._ensure_cache()
+        base, outputscale = self._base_and_outputscale()
+        holder = []
+        tx, ty, linv, linv_t, alpha, kinv, factors = _condition_cache(self, base, outputscale, float(self.noise.detach()),
+                                                                      float(self.mean_constant.detach()), X, Y, holder)
+        new = SingleTaskGP(tx, ty, self.covar_module, noise_prior=self.noise_prior, noise_lower_bound=self.noise_lower_bound)
+        new.raw_noise, new.mean_constant = self.raw_noise, self.mean_constant
+        _install_caches(new, (linv, alpha, mu), linv_t, kinv, factors)
+        holder.append(new)
+        return new
 
 
 def fit_gpytorch_model(model, maxiter=200, fast=True):

@@ -1431,6 +1431,65 @@ def gp_posterior_joint(kstar, kss, linv, alpha, mean, outputscale, inplace=True)
     return out[0], out[1], cov
 
 
+def _gp_condition_message(st):
+    return (f"gabo_gp_condition: the covariance extended by new point #{st[1]} is not positive definite (lambda^2 = outputscale k(x, x) + noise "
+            f"- l.l <= 0 or not finite)")
+
+
+def gp_condition(linv, alpha, kcross, knew, y_new=None, outputscale=1.0, noise=1e-2, mean=0.0, kinv=None, want_linv_t=True, on_fail=None):
+    """The prediction cache (linv = L^-1 n x n, alpha = Ky^-1 (y - mean), kinv = Ky^-1 or None) extended by t new points without a new
+    factorisation (gabo_gp_condition: bordered O(n^2) updates, 1 + 3 t launches, no host synchronisation): kcross t x n and knew t x t BASE
+    kernel values (new x train, new x new; the lower triangle and the diagonal of knew are read), y_new the t targets or None for the
+    believer (the current posterior mean at each new point in turn: alpha[:n] is then copied untouched and alpha[n:] = 0)
+    -> (linv, linv_t or None, alpha, kinv or None, y_used (t,)) for the n + t points, new tensors.  t <= GABO_GP_CONDITION_MAX_T,
+    n + t <= GABO_GP_MLL_LARGE_MAX_N.  All tensors fp64 on one HIP device.  A new point that leaves the matrix not positive definite
+    raises RuntimeError at the next check_deferred(), as gp_factor(defer_check=True) does; on_fail is called before that."""
+    lib = _lib.load()
+    given = [("linv", linv), ("alpha", alpha), ("kcross", kcross), ("knew", knew)] + ([("y_new", y_new)] if y_new is not None else []) \
+        + ([("kinv", kinv)] if kinv is not None else [])
+    for name, t_ in given:
+        if not torch.is_tensor(t_) or not t_.is_cuda or t_.dtype != torch.float64:
+            raise ValueError(f"gp_condition: {name} must be an fp64 tensor on a HIP device")
+    dev = linv.device
+    if any(t_.device != dev for _, t_ in given):
+        raise ValueError("gp_condition: all tensors must be on one HIP device")
+    if kcross.dim() != 2 or knew.dim() != 2 or linv.dim() != 2:
+        raise ValueError(f"gp_condition: linv must be n x n, kcross t x n and knew t x t (one set of new points), got {tuple(linv.shape)}, "
+                         f"{tuple(kcross.shape)} and {tuple(knew.shape)}")
+    t, n = kcross.shape
+    if tuple(linv.shape) != (n, n) or tuple(knew.shape) != (t, t) or alpha.numel() != n or (y_new is not None and y_new.numel() != t) \
+            or (kinv is not None and tuple(kinv.shape) != (n, n)):
+        raise ValueError(f"gp_condition: linv {tuple(linv.shape)}, alpha {tuple(alpha.shape)}, kcross {tuple(kcross.shape)}, knew {tuple(knew.shape)}"
+                         f"{'' if y_new is None else f', y_new {tuple(y_new.shape)}'}{'' if kinv is None else f', kinv {tuple(kinv.shape)}'} "
+                         f"do not belong together")
+    if not (1 <= n and 1 <= t <= _lib.GABO_GP_CONDITION_MAX_T and n + t <= _lib.GABO_GP_MLL_LARGE_MAX_N):
+        raise ValueError(f"gp_condition: n = {n}, t = {t} outside 1 <= n, 1 <= t <= {_lib.GABO_GP_CONDITION_MAX_T}, "
+                         f"n + t <= {_lib.GABO_GP_MLL_LARGE_MAX_N}")
+    li, al, kc, kn = linv.contiguous(), alpha.contiguous(), kcross.contiguous(), knew.contiguous()
+    yn = None if y_new is None else y_new.reshape(-1).contiguous()
+    ki = None if kinv is None else kinv.contiguous()
+    m = n + t
+    # one allocation for the outputs and the workspace: [L^-1 | L^-T | A | alpha | y_used | workspace]
+    wsb = int(lib.gabo_gp_condition_workspace_bytes(n, t))
+    parts = [m * m, m * m if want_linv_t else 0, m * m if ki is not None else 0, m, t, wsb // 8]
+    flat = torch.empty(sum(parts), dtype=torch.float64, device=dev)
+    cuts = [0]
+    for p in parts:
+        cuts.append(cuts[-1] + p)
+    linv_o, linv_t_o, kinv_o, alpha_o, y_used, ws = (flat[a:b] if b > a else None for a, b in zip(cuts[:-1], cuts[1:]))
+    linv_o, linv_t_o, kinv_o = (None if v is None else v.view(m, m) for v in (linv_o, linv_t_o, kinv_o))
+    ptr = lambda t_: None if t_ is None else t_.data_ptr()   # noqa: E731
+    status = _status_word(dev, force=True)
+    with _on(dev):
+        rc = lib.gabo_gp_condition(li.data_ptr(), al.data_ptr(), ptr(ki), n, kc.data_ptr(), kn.data_ptr(), ptr(yn), t, float(outputscale),
+                                   float(noise), float(mean), linv_o.data_ptr(), ptr(linv_t_o), alpha_o.data_ptr(), ptr(kinv_o),
+                                   y_used.data_ptr(), ws.data_ptr(), wsb, status.data_ptr(), _stream_ptr(dev))
+    _lib.check(rc, "gabo_gp_condition")
+    # (read back whatever set_error_checking says, at the caller's next synchronisation point: as gp_factor(defer_check=True))
+    _raise_if_not_spd(status, "gabo_gp_condition", message=_gp_condition_message, on_fail=on_fail, force=True)
+    return linv_o, linv_t_o, alpha_o, kinv_o, y_used
+
+
 _MVN_MESSAGE = ("gabo_mvn_sample: the covariance matrix is not positive definite (no Cholesky factor with a jitter of 0, 1e-8, 1e-7 or 1e-6 "
                 "on the diagonal)")
 

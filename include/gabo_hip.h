@@ -344,6 +344,36 @@ int gabo_mvn_sample(const double* mean, const double* cov, int64_t m, int64_t sa
 int gabo_mvn_base_samples(double* out, int64_t samples, int64_t m, uint64_t seed, gabo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The prediction cache of n training points extended by t new ones without a new factorisation ([3P] gpytorch's prediction strategy
+ * behind condition_on_observations / get_fantasy_model): the other half of the exact prediction above, and what a greedy
+ * batch of q proposals ("Kriging believer", Ginsbourger et al. 2010) conditions on between its sweeps.  fp64, no host synchronisation
+ * (csrc/gp_condition.hip).
+ *   linv (n x n row-major, only its lower triangle is read), alpha (n), kinv (n x n, or NULL): the cache of gabo_gp_factor or of any other
+ *   factorisation of Ky = outputscale k + noise I;
+ *   kcross: t x n BASE kernel values k(x_new_i, x_j);  knew: t x t BASE kernel matrix of the new points (lower triangle and diagonal read);
+ *   y_new: their t targets, or NULL for the believer: y_j = the posterior mean at x_new_j given everything before it.
+ * For each new point j in order, with N = n + j points in the cache, c = outputscale [kcross_j, knew_j,0..j-1], kappa = outputscale knew_jj + noise:
+ *   l = L^-1 c,  lambda^2 = kappa - l.l,  u = L^-T l;    new row of L^-1: [-u^T / lambda, 1 / lambda];
+ *   gamma = (y_j - mean - c.alpha) / lambda^2,  alpha <- [alpha - gamma u ; gamma];
+ *   A <- [[A + u u^T / lambda^2, -u / lambda^2], [-u^T / lambda^2, 1 / lambda^2]].
+ * With y_new == NULL gamma is exactly 0: the first N entries of alpha are copied untouched and the appended one is an exact 0.
+ * Outputs, dense (n + t) x (n + t) row-major (distinct from the inputs): linv_out and linv_t_out (may be NULL) with exact zeros outside their
+ * triangle, linv_t_out the transpose bit for bit; alpha_out (n + t); kinv_out (NULL exactly when kinv is NULL) exactly symmetric;
+ * y_out (t): the targets used.  Every sum runs over the training index in ascending order with a fixed tree: the bits of a result depend
+ * neither on the grid nor on t (one call with t points = t calls with one).  1 + 3 t launches.
+ * status: int[2] ON THE DEVICE, zeroed by the caller: {GABO_ERR_NOT_SPD, j} for the first new point j whose lambda^2 is not positive and
+ * finite (outputs then unspecified; nothing faults).
+ * workspace: *_workspace_bytes(n, t) = (2 (n + t) + 8) doubles (0 for arguments that are refused).
+ * GABO_ERR_DIM for t > GABO_GP_CONDITION_MAX_T or n + t > GABO_GP_MLL_LARGE_MAX_N; GABO_ERR_ARG for n < 1, t < 1, a null pointer other than
+ * kinv / kinv_out / linv_t_out / y_new, kinv without kinv_out or the reverse, or a workspace smaller than that - all before any HIP call. */
+#define GABO_GP_CONDITION_MAX_T 16
+size_t gabo_gp_condition_workspace_bytes(int64_t n, int64_t t);
+int gabo_gp_condition(const double* linv, const double* alpha, const double* kinv, int64_t n, const double* kcross, const double* knew,
+                      const double* y_new, int64_t t, double outputscale, double noise, double mean, double* linv_out, double* linv_t_out,
+                      double* alpha_out, double* kinv_out, double* y_out, void* workspace, size_t workspace_bytes, int* status,
+                      gabo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * One evaluation of the surrogate-fit objective of HD-GaBO with its gradient, as one HOST call (it returns with the numbers):
  * the marginal log likelihood of ScaleKernel(NestedSpdLogEuclideanGaussianKernel) at a projection matrix W and scalar hyper-parameters.
  * Replaces the closure fit_gpytorch_manifold differentiates by autograd   manifold_optimization/manifold_gp_fit.py:54-222
