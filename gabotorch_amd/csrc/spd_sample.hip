@@ -73,7 +73,8 @@ __global__ __launch_bounds__(64) void spd_sample_kernel(double* __restrict__ out
 
 
 // The same sampler for d <= 8 with the matrix in the lane's REGISTERS (compile-time indices): the draws, their order and every arithmetic statement
-// are those of spd_sample_kernel above - same stream, same bits - without the LDS round trip of each of its ~10 d^3 accesses (the kernel is one
+// are those of spd_sample_kernel above - same stream, same bits (the two forms never meet at one d: each is held to the numpy restatement of this
+// file, oracle.selection.spd_samples, at every d it serves by tests/test_gpu_spd_sampler.py) - without the LDS round trip of each of its ~10 d^3 accesses (the kernel is one
 // dependent chain per lane: 26 us for 256 matrices of order 5 under rocprofv3, on the critical path of an acquisition sweep between its set-up and
 // its scoring launch).
 template <int D>

@@ -1,8 +1,10 @@
 """The oracle of the device-side restart selection (oracle/selection.py): its Philox4x32-10 against the known-answer vectors published with the
 generator (Random123 kat_vectors: philox4x32, 10 rounds), and the heuristic's invariants."""
 import numpy as np
+import pytest
 
 from oracle import selection as osel
+from tests import _spd_sampler_cases as cases
 
 
 def test_philox4x32_10_known_answers():
@@ -52,3 +54,58 @@ def test_sphere_sampler_oracle_is_uniform_on_the_sphere():
     odd = osel.sphere_samples(5, 1000, 7)                                              # odd dimension: the second deviate of the last pair is dropped
     np.testing.assert_allclose(np.linalg.norm(odd, axis=1), 1.0, rtol=0, atol=1e-15)
     assert odd.shape == (1000, 7) and np.abs(odd.mean(0)).max() < 0.06
+
+
+@pytest.mark.parametrize("d", cases.ORDERS)
+def test_spd_sampler_oracle_has_the_spectrum_it_drew(d):
+    """oracle.selection.spd_samples at every order the device sampler takes, both seeds of the device test: X is symmetric with the eigenvalues
+    lam (so Q is orthogonal to the working precision), lam lies in [min_eig, max_eig], kappa >= 1 (= 1 exactly when there is one column)"""
+    for seed in cases.SEEDS:
+        X, lam, kappa = cases.oracle(seed, 0, cases.N, d)
+        assert X.shape == (cases.N, d, d) and lam.shape == (cases.N, d) and kappa.shape == (cases.N,)
+        np.testing.assert_array_equal(X, X.transpose(0, 2, 1))
+        assert lam.min() >= cases.LO and lam.max() <= cases.HI
+        np.testing.assert_allclose(np.linalg.eigvalsh(X), np.sort(lam, axis=1), rtol=0, atol=cases.spectrum_bound(d))
+        assert kappa.min() >= 1.0 and np.isfinite(kappa).all() and (d > 1 or (kappa == 1.0).all())
+    # equal bounds: every sample is that multiple of the identity
+    X, lam, _ = cases.oracle(cases.SEEDS[0], 0, 5, d, 2.0, 2.0)
+    np.testing.assert_array_equal(lam, 2.0)
+    np.testing.assert_allclose(X, np.broadcast_to(2.0 * np.eye(d), X.shape), rtol=0, atol=16 * d * cases.EPS * 2.0)
+
+
+def test_spd_sampler_oracle_is_addressed_by_seed_and_sample_index():
+    """sample i depends on (64-bit seed, 64-bit index first + i) only: overlapping ranges agree bit for bit, also across the counter's low word; the
+    high word of the counter and the high word of the key each change the draw"""
+    seed = cases.SEEDS[1]
+    for d in (3, 10):
+        whole = cases.oracle(seed, 0, cases.N, d)
+        part = osel.spd_samples(seed, 37, 50, d, cases.LO, cases.HI)
+        for a, b in zip(whole, part):
+            np.testing.assert_array_equal(a[37:87], b)
+        high = cases.oracle(seed, cases.FIRST_HIGH, 8, d)                   # indices 2^32 - 3 ... 2^32 + 4
+        tail = osel.spd_samples(seed, 2 ** 32 + 1, 6, d, cases.LO, cases.HI)    # 2^32 + 1 ... 2^32 + 6
+        for a, b in zip(high, tail):
+            np.testing.assert_array_equal(a[4:8], b[:4])
+        # index 2^32 + i is not index i (a counter cut to its low word would say so)
+        assert np.abs(high[0][3:8] - whole[0][0:5]).max() > 0.1 and np.abs(high[1][3:8] - whole[1][0:5]).max() > 0.01
+        # nor is seed + 2^32 the seed (a key cut to its low word), nor the low word alone
+        for other in (seed ^ (1 << 32), seed & 0xFFFFFFFF, seed ^ (1 << 63)):
+            assert np.abs(osel.spd_samples(other, 0, 5, d, cases.LO, cases.HI)[0] - whole[0][:5]).max() > 0.1
+    assert np.abs(cases.oracle(0, 0, cases.N, 4)[0] - cases.oracle(1 << 32, 0, cases.N, 4)[0]).max() > 0.1
+
+
+def test_spd_sampler_oracle_in_double_stays_within_a_quarter_of_the_device_bound():
+    """The reference against itself: the same statements in plain double with numpy's libm (log, cos, sin a few ulp from the correctly rounded values,
+    like the device's) against the extended-precision run, for EVERY case the device is compared on - per sample within a quarter of the bound the
+    device gets, 16 d eps kappa_i max_eig / 4.  (Where np.longdouble is no wider than double the two runs differ by libm's 2 pi only.)"""
+    worst = 0.0
+    for seed, first, count, d in cases.CASES:
+        X, lam, kappa = cases.oracle(seed, first, count, d)
+        Xd, lamd, kappad = osel.spd_samples(seed, first, count, d, cases.LO, cases.HI, work=np.float64)
+        err = np.abs(Xd - X).reshape(count, -1).max(1)
+        ratio = err / (0.25 * cases.bound(d, kappa))
+        worst = max(worst, float(ratio.max()))
+        assert (ratio <= 1.0).all(), (hex(seed), first, d, int(np.argmax(ratio)), float(ratio.max()), float(kappa[np.argmax(ratio)]))
+        np.testing.assert_allclose(lamd, lam, rtol=0, atol=4 * cases.EPS * cases.HI)
+        np.testing.assert_allclose(kappad, kappa, rtol=1e-6)
+    print(f"double-precision oracle against the extended one: worst error / (bound / 4) = {worst:.3f}")
