@@ -12,6 +12,8 @@
 
 #ifndef GABO_PAIR_WAVES
 #define GABO_PAIR_WAVES 2  /* waves per SIMD the pairwise kernel is register-budgeted for */
+#else
+#define GABO_PAIR_WAVES_FORCED 1  /* A/B builds: one budget for every instantiation (spd_pair_gauss_only_waves) */
 #endif
 
 namespace gabo {
@@ -40,7 +42,107 @@ struct SpdGcolPointer {
     __device__ __forceinline__ double operator[](int k) const { return p[(int64_t)k * stride]; }
 };
 
-template <int D, int ORIENT = kQlOrientPerLane, int CTL = kQlCtlPlain, class GCOL>
+// The staged form of the congruence (ai_sumsq with AHEAD > 0): for an instantiation budgeted for more waves per SIMD than the compiler's own
+// schedule of the congruence fits (spd_pair_gauss_only_waves).  Left alone, the scheduler takes the row of W once, from its last row to its
+// first, and to do so issues most of the 55 loads of G at the top of the pair and holds their destinations beside the growing m[] (194 VGPRs at
+// d = 10); squeezed by the register budget alone it gives vector registers back by stretching the scalar live ranges of the W row until they spill
+// to lanes (117 scalar spills, 346 lane moves per pair).  Here both operands arrive in stages, and scheduling barriers keep the stages apart:
+//   G  column by column, AHEAD columns in front of the column being consumed;
+//   W  in groups of consecutive rows of one column's products, at most WLIM doubles a group, one group in front of the group being consumed.  An
+//      entry W[r][k] serves the columns 0 .. k and is read again for each (from the scalar cache: 220 doubles per pair at d = 10 instead of 55),
+//      so that no more than two groups are ever live in scalar registers.  Scalar loads return out of order - a wait on one is a wait on all -
+//      so a group is waited for BEFORE the next one is issued.
+// The arithmetic - every operation, its operands and the order along every sum - is that of the plain form.
+template <int D, int WLIM>
+struct SpdWGroups {
+    int n = 0;
+    int col[tri_size(D)] = {}, r0[tri_size(D)] = {}, r1[tri_size(D)] = {};      // group g: rows r0 .. r1 - 1 of column col, columns descending
+    constexpr SpdWGroups() {
+        static_assert(WLIM >= D, "a row of the first column must fit a group");
+        for (int c = D - 1; c >= 0; --c) {
+            for (int r = c; r < D;) {
+                int sum = 0;
+                col[n] = c, r0[n] = r;
+                while (r < D && sum + (r - c + 1) <= WLIM) sum += r - c + 1, ++r;
+                r1[n++] = r;
+            }
+        }
+    }
+};
+#ifndef GABO_PAIR_WLIM
+#define GABO_PAIR_WLIM 16
+#endif
+template <int D, int AHEAD, class GCOL>
+__device__ __forceinline__ void ai_congruence_staged(const double* __restrict__ W, const GCOL& Gj, double (&m)[tri_size(D)]) {
+    constexpr SpdWGroups<D, (GABO_PAIR_WLIM < D ? D : GABO_PAIR_WLIM)> kG{};
+    double gq[D][D];         // gq[col][k - col] = G[k][col]: at most AHEAD + 1 columns live
+    double wq[2][D][D];      // wq[group & 1][r][k] = W[r][k]
+    double c[D];             // the current column of C, c[r - col]
+    auto issue_g = [&](auto ss) {
+        constexpr int col = D - 1 - decltype(ss)::value;
+        static_for<D - col>([&](auto kk) { gq[col][decltype(kk)::value] = Gj[tri(col + decltype(kk)::value, col)]; });
+    };
+    auto issue_w = [&](auto gg) {
+        constexpr int g = decltype(gg)::value, col = kG.col[g], r0 = kG.r0[g], r1 = kG.r1[g];
+        // a group's loads are its own, not merged with an earlier group's of the same entries: a laundered pointer - in the CONSTANT address
+        // space, or the loads behind it become flat loads into vector registers (see spd_gcol_ptr)
+        typedef const double __attribute__((address_space(4)))* wrow_ptr;
+        wrow_ptr Wg = (wrow_ptr)W;
+        asm volatile("" : "+s"(Wg));
+        static_for<r1 - r0>([&](auto rr) {
+            constexpr int r = r0 + decltype(rr)::value;
+            static_for<r - col + 1>([&](auto kk) { wq[g & 1][r][col + decltype(kk)::value] = Wg[tri(r, col + decltype(kk)::value)]; });
+        });
+    };
+    static_for<(AHEAD < D ? AHEAD : D)>(issue_g);
+    issue_w(std::integral_constant<int, 0>{});
+    static_for<kG.n>([&](auto gg) {
+        constexpr int g = decltype(gg)::value, col = kG.col[g], r0 = kG.r0[g], r1 = kG.r1[g];
+        if constexpr (r0 == col && D - 1 - col + AHEAD < D) issue_g(std::integral_constant<int, D - 1 - col + AHEAD>{});
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): group g of W has arrived
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (g + 1 < kG.n) issue_w(std::integral_constant<int, g + 1>{});
+        static_for<r1 - r0>([&](auto rr) {
+            constexpr int r = r0 + decltype(rr)::value;
+            double acc = wq[g & 1][r][col] * gq[col][0];
+            static_for<r - col>([&](auto kk) {
+                constexpr int k = col + 1 + decltype(kk)::value;
+                acc = __builtin_fma(wq[g & 1][r][k], gq[col][k - col], acc);
+            });
+            c[r - col] = acc;
+        });
+        // the column's rank-1 update once the column of C is whole and the column of G dead (updating row by row would hold G's column beside
+        // the entries of M that column 0 creates: 20 registers more at the peak); entry (r, q) of M is first touched by column q
+        if constexpr (r1 == D) {
+            __builtin_amdgcn_sched_barrier(0);
+            static_for<D - col>([&](auto rr) {
+                constexpr int r = col + decltype(rr)::value;
+                static_for<r - col + 1>([&](auto qq) {
+                    constexpr int q = col + decltype(qq)::value;
+                    m[tri(r, q)] = col == q ? c[r - col] * c[q - col] : __builtin_fma(c[r - col], c[q - col], m[tri(r, q)]);
+                });
+            });
+        }
+    });
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// The constants of log_tab by one scalar load per pair, behind the eigenvalue iteration, where the scalar registers are free.  LogTabRegs::load()
+// pins them in vector registers, and the compiler forms them once, in front of the row loop: 16 registers held across the whole pair, which
+// the staged form's budget does not have.  The same eight doubles.
+__constant__ double kLogTabRegs[8] = {1.41421356237309504880, 1.0 / 7.0, -1.0 / 6.0, 0.2, -0.25, 1.0 / 3.0, 6.93147180369123816490e-01,
+                                      1.90821492927058770002e-10};
+__device__ __forceinline__ LogTabRegs log_tab_regs_scalar() {
+    typedef const double __attribute__((address_space(4)))* const_ptr;
+    const_ptr p = (const_ptr)kLogTabRegs;
+    asm volatile("" : "+s"(p));
+    LogTabRegs t;
+    t.sqrt2 = p[0], t.c7 = p[1], t.c6 = p[2], t.c5 = p[3], t.c4 = p[4], t.c3 = p[5], t.ln2_hi = p[6], t.ln2_lo = p[7];
+    return t;
+}
+
+template <int D, int ORIENT = kQlOrientPerLane, int CTL = kQlCtlPlain, int AHEAD = 0, class GCOL>
 __device__ __forceinline__ double ai_sumsq(const double* __restrict__ W, const GCOL& Gj, const double* __restrict__ ltab, const double eps2 = 0.0) {
     constexpr int T = tri_size(D);
     // Column `col` of C = W G depends only on column `col` of G:  C[r][col] = sum_{k=col..r} W[r][k] G[k][col].
@@ -51,6 +153,10 @@ __device__ __forceinline__ double ai_sumsq(const double* __restrict__ W, const G
     // and 208 lane moves in the pair body and 233 VGPRs, in descending order none and 194 - against 216 for the other two orientations.)
     constexpr bool kDescending = ORIENT == kQlOrientLast;
     double m[T];
+    if constexpr (AHEAD > 0) {
+        static_assert(kDescending, "the staged congruence takes the columns from the last to the first");
+        ai_congruence_staged<D, AHEAD>(W, Gj, m);
+    } else
     static_for<D>([&](auto cc) {
         constexpr int col = kDescending ? D - 1 - decltype(cc)::value : decltype(cc)::value;
         double g[D - col], c[D - col];
@@ -78,7 +184,7 @@ __device__ __forceinline__ double ai_sumsq(const double* __restrict__ W, const G
     tridiagonalize<D, ORIENT>(m, dg, e2);
     tridiag_eigenvalues<D, ORIENT, CTL>(dg, e2, eps2);
     double s = 0.0;
-    const LogTabRegs lr = LogTabRegs::load();
+    const LogTabRegs lr = AHEAD > 0 ? log_tab_regs_scalar() : LogTabRegs::load();
     static_for<D>([&](auto kk) { double lg = log_tab(dg[decltype(kk)::value], lr, ltab); s = __builtin_fma(lg, lg, s); });
     return s;
 }
@@ -176,8 +282,24 @@ constexpr int spd_pair_gauss_only_sweepctl(int d) { return d == 20 ? kQlCtlPlain
 #else
 constexpr int spd_pair_gauss_only_sweepctl(int d) { return GABO_PAIR_SWEEPCTL; }      // (A/B builds: one form for every dimension)
 #endif
+// Waves per SIMD the Gaussian-only instantiation is register-budgeted for (the general instantiation keeps GABO_PAIR_WAVES), and how many
+// columns of G its congruence loads ahead (ai_sumsq's AHEAD; 0: the compiler's own schedule).  Two waves leave the vector pipe 93.7 % busy at
+// d = 10 (194 VGPRs), three 97.5 % at d = 9 (168 VGPRs: the last dimension the compiler fits by itself; profiles/waves3_pmc_busy.txt).  The budget
+// alone does not buy the third wave at d = 10: -DGABO_PAIR_WAVES=3 on the plain form gives 168 VGPRs with 117 scalar spills, 346 lane moves per
+// pair and 44 bytes of scratch, and measures 1.7 % slower (2.160 -> 2.197 ms).  With the staged congruence the body needs 164, nothing spills, and
+// the N = 4096 Gram goes 2.188 -> 2.142 and 2.118 -> 2.073 ms in two jobs, the same bits (profiles/waves3_ab_bench.txt).  d = 11 (232) is out of reach of this alone.
+#ifndef GABO_PAIR_WAVES_FORCED
+constexpr int spd_pair_gauss_only_waves(int d) { return d > GABO_PAIR_TWO_WAVE_MAX_DIM ? 1 : (d == 10 ? 3 : GABO_PAIR_WAVES); }
+#else
+constexpr int spd_pair_gauss_only_waves(int d) { return d > GABO_PAIR_TWO_WAVE_MAX_DIM ? 1 : GABO_PAIR_WAVES; }      // (A/B builds)
+#endif
+#ifndef GABO_PAIR_AHEAD
+constexpr int spd_pair_gauss_only_ahead(int d) { return d == 10 && spd_pair_gauss_only_waves(d) == 3 ? 2 : 0; }
+#else
+constexpr int spd_pair_gauss_only_ahead(int d) { return d == 10 ? GABO_PAIR_AHEAD : 0; }      // (A/B builds)
+#endif
 template <int D, bool GAUSS_ONLY, bool BUFFER_ONLY>
-__global__ __launch_bounds__(256, (D > GABO_PAIR_TWO_WAVE_MAX_DIM ? 1 : GABO_PAIR_WAVES)) void spd_ai_pairwise_kernel(const double* __restrict__ Winv, const double* __restrict__ G,
+__global__ __launch_bounds__(256, (GAUSS_ONLY ? spd_pair_gauss_only_waves(D) : (D > GABO_PAIR_TWO_WAVE_MAX_DIM ? 1 : GABO_PAIR_WAVES))) void spd_ai_pairwise_kernel(const double* __restrict__ Winv, const double* __restrict__ G,
                                                               double* __restrict__ out, double* __restrict__ dist_out_arg,
                                                               int64_t n1, int64_t n2,
                                                               int64_t w_batch_stride, int64_t g_batch_stride, int rows,
@@ -284,7 +406,7 @@ __global__ __launch_bounds__(256, (D > GABO_PAIR_TWO_WAVE_MAX_DIM ? 1 : GABO_PAI
             SpdGcolBuffer gb = gbuf;
             asm volatile("" : "+v"(gb.voff));                  // the 55 G loads stay inside the row loop (see the general loop below)
             asm volatile("" : "+s"(gb.stride_bytes));
-            const double s = ai_sumsq<D, spd_pair_gauss_only_orientation(D), spd_pair_gauss_only_sweepctl(D)>(W, gb, ltab, eps2);
+            const double s = ai_sumsq<D, spd_pair_gauss_only_orientation(D), spd_pair_gauss_only_sweepctl(D), spd_pair_gauss_only_ahead(D)>(W, gb, ltab, eps2);
             double val;
             if constexpr (kTabExp) {
                 val = exp_neg_tab(-((s + 1e-15) * beta), ec, ec3, tab);

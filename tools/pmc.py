@@ -1,4 +1,4 @@
-"""PMC passes of one kernel (GPU box): python tools/pmc.py <kernel-name-substring> <out.json> -- <command ...>
+"""PMC passes of one kernel (GPU box): python tools/pmc.py <kernel-name-substring> <out.json> [--sets 0,2] -- <command ...>
 One rocprofv3 run per counter set (--kernel-trace only next to --pmc, as the pool requires); averages over the matching dispatches."""
 import collections, csv, glob, json, os, shutil, subprocess, sys
 
@@ -15,7 +15,11 @@ def main():
     cmd = sys.argv[sys.argv.index("--") + 1:]
     res = {}
     env = dict(os.environ, TMPDIR="/tmp")
+    head = sys.argv[3:sys.argv.index("--")]
+    only = [int(v) for v in head[head.index("--sets") + 1].split(",")] if "--sets" in head else range(len(SETS))
     for k, cs in enumerate(SETS):
+        if k not in only:
+            continue
         d = f"/tmp/pmc_{os.getpid()}_{k}"
         shutil.rmtree(d, ignore_errors=True)
         r = subprocess.run(["rocprofv3", "--pmc", *cs.split(), "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "out", "--"] + cmd,
