@@ -114,6 +114,8 @@ SIGNATURES = {
     "gabo_sphere_ktable_build": (_I, [_D, _P, _P]),
     "gabo_sphere_pairwise_cached": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, _I64, _I64, _D, _I, _I, _P, _P]),
     "gabo_sphere_from_inner": (_I, [_P, _P, _I64, _D, _I, _I, _P]),
+    "gabo_sphere_zonal_from_inner": (_I, [_P, _P, _I64, _P, _I, _I, _P]),
+    "gabo_sphere_zonal_pairwise": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, _I64, _I64, _P, _I, _I, _I, _I, _P]),
     "gabo_spd_manifold_op": (_I, [_I, _P, _P, _P, _P, _P, _P, _I64, _I, _P, _P]),
     "gabo_spd_project": (_I, [_P, _P, _P, _I64, _I, _I, _P]),
     "gabo_spd_logm_mandel": (_I, [_P, _P, _I64, _I, _P]),

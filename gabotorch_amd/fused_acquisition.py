@@ -32,10 +32,11 @@ def _surrogate_view(gp):
 
 
 class FusedAcquisition:
-    def __init__(self, acq, family, mode, beta, matrix_input, device, flavour="ai", view=None):
+    def __init__(self, acq, family, mode, beta, matrix_input, device, flavour="ai", view=None, zonal=None):
         base, outputscale, mean, (linv, alpha), train_x = view if view is not None else _surrogate_view(acq.model)
         self.family, self.mode, self.beta, self.matrix_input = family, mode, beta, matrix_input
         self.flavour = flavour          # SPD kernels: "ai" affine-invariant, "le" log-Euclidean, "frob" Frobenius
+        self.zonal = None               # sphere Matern / heat kernel: the host's series of f and f' (`beta` is the lengthscale, `mode` unused)
         self.kind = _lib.GABO_ACQ_EXPECTED_IMPROVEMENT if isinstance(acq, models.ExpectedImprovement) else _lib.GABO_ACQ_POSTERIOR_MEAN
         self.maximize = bool(acq.maximize)
         self.best_f = float(getattr(acq, "best_f", 0.0))
@@ -65,6 +66,11 @@ class FusedAcquisition:
             # one launch per evaluation for the sphere kernels too (csrc/sphere_tr.hip); needs the training set in both layouts
             n_tr, dim_tr = self.train.shape
             self.single_launch = (7 * n_tr + 6 * dim_tr) * 8 <= 150 * 1024 and n_tr <= 4096 and 2 <= dim_tr <= 512
+            if zonal is not None:
+                # no single-launch evaluator for the series kernels (csrc/sphere_tr.hip knows the geodesic kernels only): the lock-step plan
+                nu, num_levels = zonal
+                self.single_launch = False
+                self.zonal = tuple(ops.sphere_matern_coefficients(dim_tr, beta, nu, num_levels, order) for order in (0, 1))
             self.train_t = self.train.t().contiguous() if self.single_launch else None
         self.metric = {"ai": _lib.GABO_METRIC_AFFINE_INVARIANT, "le": _lib.GABO_METRIC_LOG_EUCLIDEAN, "frob": _lib.GABO_METRIC_FROBENIUS}[flavour]
         self.train_factors = None
@@ -87,6 +93,8 @@ class FusedAcquisition:
         elif family == "spd":
             # d(X, X)^2 = 1e-15 exactly (the eigenvalues of L^-1 X L^-T are 1 to rounding): spd_utils_torch.py:120
             self.kxx = math.exp(-beta * (1e-15 if mode == _lib.GABO_OUT_GAUSSIAN else math.sqrt(1e-15)))
+        elif self.zonal is not None:
+            self.kxx = float(self.zonal[0][0].sum())       # f(1) = sum p_n (P_n(1) = 1), as the host computed the p_n
         else:
             # <x, x> is clamped to 1 - 1e-15 (sphere_utils_torch.py:53): d(x, x) = acos(1 - 1e-15)
             t0 = math.acos(1.0 - 1e-15)
@@ -141,7 +149,17 @@ class FusedAcquisition:
                 ls = float(k.lengthscale.double())
                 mode, beta = _lib.GABO_OUT_LAPLACE, 1.0 / (ls * ls)
             return FusedAcquisition(acq, "sphere", mode, beta, False, device)
+        if type(k) is kernels_sphere.SphereRiemannianMaternKernel:
+            if post_processing is not None:
+                return None
+            return FusedAcquisition(acq, "sphere", None, float(k.lengthscale.double()), False, device, zonal=(k.nu, k.num_levels))
         return None
+
+    def _sphere_f(self, c, order):
+        """f^(order) on the inner products c: the geodesic kernels' closed forms, or the series of the Matern / heat kernel"""
+        if self.zonal is not None:
+            return ops.sphere_zonal_from_inner(c, *self.zonal[order])
+        return ops.sphere_from_inner(c, self.beta, self.mode, order)
 
     def _strip(self, x):
         pts = ops.matrix_to_mandel(x) if self.matrix_input else x.contiguous()
@@ -151,7 +169,7 @@ class FusedAcquisition:
             feat = ops.spd_logm_mandel(pts) if self.flavour == "le" else pts
             return pts, ops.frobenius_pairwise(feat, self.train_feat, self.beta, self.mode), feat
         c = pts @ self.train.t()
-        return pts, ops.sphere_from_inner(c, self.beta, self.mode, 0), c
+        return pts, self._sphere_f(c, 0), c
 
     def egrad_mandel(self, pts, active_ptr=None, out=None):
         """Euclidean gradient of the cost at SPD points given (and returned) as Mandel vectors: the chain without the two
@@ -220,5 +238,5 @@ class FusedAcquisition:
         if self.family == "spd":
             g = self._strip_backward(pts, c, gk)         # (c = the per-point features of the log-Euclidean / Frobenius flavours)
         else:
-            g = (gk * ops.sphere_from_inner(c, self.beta, self.mode, 1)) @ self.train
+            g = (gk * self._sphere_f(c, 1)) @ self.train
         return val, (ops.mandel_to_matrix(g) if self.matrix_input else g)

@@ -606,6 +606,168 @@ def sphere_kernel(x1, x2, beta, mode=_lib.GABO_OUT_GAUSSIAN, diag=False):
     return _SphereFromInner.apply(c, beta, int(mode), 0).to(x1.device)
 
 
+# ---- Riemannian Matern / heat kernels on the sphere: zonal series with non-negative coefficients (csrc/sphere_zonal.hip) ----------
+SPHERE_ZONAL_MAX_LEVELS = 128
+
+
+def _zonal_derivative(coeff, series_dim):
+    """d/dc of sum_k coeff[k] P_k^(d): coefficients coeff[k] k (k + d - 1) / d, k >= 1, of the series in dimension d + 2"""
+    import numpy as np
+    k = np.arange(1, len(coeff), dtype=np.float64)
+    out = coeff[1:] * (k * (k + (series_dim - 1.0))) / float(series_dim)
+    return (out if len(out) else np.zeros(1)), series_dim + 2
+
+
+def sphere_matern_coefficients(dim, lengthscale, nu, num_levels, order=0, wrt_lengthscale=False):
+    """Coefficients of the Riemannian Matern kernel (nu = math.inf: the heat kernel) on the unit sphere of R^dim (Borovitskiy et al. 2020),
+    truncated at `num_levels`, as a zonal series  k(x, y) = sum_n p_n P_n(<x, y>):  with d = dim - 1, lambda_n = n (n + d - 1), m_n the number of
+    spherical harmonics of level n,  p_n = Phi(lambda_n) m_n / sum_k Phi(lambda_k) m_k,
+        Phi = (2 nu / kappa^2 + lambda)^(-nu - d/2)   or   exp(-kappa^2 lambda / 2),   kappa = lengthscale.
+    p_n >= 0 and sum p_n = 1: positive definite for every kappa, k(x, x) = 1.  A lengthscale well below 1 / num_levels is not resolved.
+    order = 1, 2: the series of the first / second derivative in c = <x, y>; wrt_lengthscale: of the derivative in kappa (order 0: they sum to 0).
+    -> (numpy float64 coefficients, series_dim) for sphere_zonal_from_inner / sphere_zonal_pairwise.  Host arithmetic only: the weights are
+    formed in log space (m_n from exact integers) relative to the largest one, so nothing overflows at dim 64 or 128 levels."""
+    import math
+
+    import numpy as np
+    dim, L, order = int(dim), int(num_levels), int(order)
+    kappa, nu = float(lengthscale), float(nu)
+    if dim < 2:
+        raise ValueError(f"sphere_matern_coefficients: dim = {dim}; the sphere S^(dim-1) needs dim >= 2")
+    if not 1 <= L <= SPHERE_ZONAL_MAX_LEVELS:
+        raise ValueError(f"sphere_matern_coefficients: num_levels = {num_levels} outside 1 ... {SPHERE_ZONAL_MAX_LEVELS}")
+    if not nu > 0.0:
+        raise ValueError(f"sphere_matern_coefficients: nu = {nu} must be positive (math.inf: the heat kernel)")
+    if not (kappa > 0.0 and math.isfinite(kappa)):
+        raise ValueError(f"sphere_matern_coefficients: lengthscale = {kappa} must be positive and finite")
+    if order not in (0, 1, 2):
+        raise ValueError(f"sphere_matern_coefficients: order = {order} outside 0, 1, 2")
+    d = dim - 1
+    n = np.arange(L + 1, dtype=np.float64)
+    lam = n * (n + (d - 1.0))
+    logm = np.array([0.0] + [math.log(math.comb(k + d, d) - math.comb(k + d - 2, d)) for k in range(1, L + 1)])
+    if math.isinf(nu):
+        logphi = -(kappa * kappa) * lam / 2.0
+        rate = -kappa * lam                                            # Phi' / Phi
+    else:
+        base = 2.0 * nu / (kappa * kappa) + lam
+        logphi = -(nu + d / 2.0) * np.log(base)
+        rate = (nu + d / 2.0) * (4.0 * nu / kappa ** 3) / base
+    logw = logphi + logm
+    w = np.exp(logw - logw.max())
+    p = w / w.sum()
+    if wrt_lengthscale:
+        p = p * (rate - (p * rate).sum())
+    series_dim = d
+    for _ in range(order):
+        p, series_dim = _zonal_derivative(p, series_dim)
+    return np.ascontiguousarray(p, dtype=np.float64), series_dim
+
+
+def _zonal_coeff(coeff):
+    import numpy as np
+    a = np.ascontiguousarray(coeff, dtype=np.float64).reshape(-1)
+    return a, a.ctypes.data, int(a.size)
+
+
+def sphere_zonal_from_inner(inner, coeff, series_dim):
+    """Element-wise sum_k coeff[k] P_k(c) on an inner-product tensor (any shape); coeff: host float64 (see sphere_matern_coefficients)."""
+    lib = _lib.load()
+    out_device = inner.device
+    dev = _device_for(inner)
+    c = _prep(inner, dev).contiguous()
+    out = torch.empty_like(c)
+    a, ptr, na = _zonal_coeff(coeff)
+    with _on(dev):
+        _lib.check(lib.gabo_sphere_zonal_from_inner(c.data_ptr(), out.data_ptr(), c.numel(), ptr, na, int(series_dim), _stream_ptr(dev)),
+                   "gabo_sphere_zonal_from_inner")
+    return _out(out, out_device)
+
+
+def sphere_zonal_pairwise(x1, x2, coeff, series_dim, diag=False, symmetric=False):
+    """x1 (..., N1, dim), x2 (..., N2, dim) -> (..., N1, N2)   [diag: (..., N, 1)]:  sum_k coeff[k] P_k(<x1_i, x2_j>) in one launch."""
+    lib = _lib.load()
+    if x1.shape[:-2] != x2.shape[:-2] or x1.shape[-1] != x2.shape[-1]:
+        raise RuntimeError(f"batch/feature shapes differ: {tuple(x1.shape)} vs {tuple(x2.shape)}")
+    out_device = x1.device
+    dev = _device_for(x1, x2)
+    a, b = _prep(x1, dev), _prep(x2, dev)
+    dim = a.shape[-1]
+    n1, n2 = a.shape[-2], b.shape[-2]
+    if diag and n1 != n2:
+        raise RuntimeError("diag=True needs x1 and x2 of the same length")
+    bshape = a.shape[:-2]
+    a2, nb, s1 = _flatten_batch(a, 2)
+    b2, _, s2 = _flatten_batch(b, 2)
+    out = torch.empty(bshape + ((n1, 1) if diag else (n1, n2)), dtype=torch.float64, device=dev)
+    ca, ptr, na = _zonal_coeff(coeff)
+    if out.numel() == 0:
+        return _out(out, out_device)
+    flags = _lib.GABO_SYMMETRIC if symmetric and not diag else 0
+    with _on(dev):
+        rc = lib.gabo_sphere_zonal_pairwise(a2.data_ptr(), b2.data_ptr(), out.data_ptr(), nb, n1, n2, dim, s1, s2, ptr, na, int(series_dim),
+                                            flags, 1 if diag else 0, _stream_ptr(dev))
+    _lib.check(rc, "gabo_sphere_zonal_pairwise")
+    return _out(out, out_device)
+
+
+class _SphereMaternFromInner(torch.autograd.Function):
+    """f^(order)(c) of the Riemannian Matern series, differentiable in c up to order 2 (value -> gradient -> Hessian-vector product) and, at
+    order 0, in the lengthscale."""
+
+    @staticmethod
+    def forward(ctx, c, lengthscale, dim, nu, num_levels, order):
+        lval = float(lengthscale)
+        coeff, sd = sphere_matern_coefficients(dim, lval, nu, num_levels, order)
+        out = sphere_zonal_from_inner(c, coeff, sd)
+        ctx.save_for_backward(c)
+        ctx.lval, ctx.spec, ctx.order = lval, (dim, nu, num_levels), order
+        ctx.ls_shape = lengthscale.shape if torch.is_tensor(lengthscale) else None
+        ctx.ls_device = lengthscale.device if torch.is_tensor(lengthscale) else None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        c, = ctx.saved_tensors
+        dim, nu, num_levels = ctx.spec
+        gc = gl = None
+        if ctx.needs_input_grad[0]:
+            if ctx.order >= 2:
+                raise RuntimeError("gabotorch_amd sphere kernels are differentiable twice in x, not three times")
+            gc = g * _SphereMaternFromInner.apply(c, torch.tensor(ctx.lval, dtype=torch.float64), dim, nu, num_levels, ctx.order + 1)
+        if ctx.needs_input_grad[1]:
+            if ctx.order != 0:
+                raise RuntimeError("mixed x/lengthscale second derivatives of the sphere kernels are not provided")
+            with torch.no_grad():
+                coeff, sd = sphere_matern_coefficients(dim, ctx.lval, nu, num_levels, 0, wrt_lengthscale=True)
+                gl = (g * sphere_zonal_from_inner(c, coeff, sd)).sum().reshape(ctx.ls_shape).to(ctx.ls_device)
+        return gc, gl, None, None, None, None
+
+
+def sphere_matern_kernel(x1, x2, lengthscale, nu, num_levels, diag=False):
+    """Differentiable entry point of the Riemannian Matern kernel on the sphere (nu = math.inf: heat kernel), shaped like sphere_kernel.
+    Without autograd: one fused launch (the symmetric one when x1 is x2).  With autograd: the inner products are a plain batched GEMM followed
+    by the element-wise series, differentiable twice in x1 / x2 and once in the lengthscale."""
+    if torch.is_tensor(lengthscale):
+        if lengthscale.numel() != 1:
+            raise RuntimeError("gabotorch_amd sphere kernels take a single lengthscale (batch_shape == ())")
+        lengthscale = lengthscale.double()
+    else:
+        lengthscale = torch.tensor(float(lengthscale), dtype=torch.float64)
+    dim = x1.shape[-1]
+    need = torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad or lengthscale.requires_grad)
+    if not need:
+        coeff, sd = sphere_matern_coefficients(dim, float(lengthscale), nu, num_levels)
+        return sphere_zonal_pairwise(x1, x2, coeff, sd, diag=diag, symmetric=x1 is x2)
+    dev = _device_for(x1, x2)
+    a, b = x1.double().to(dev), x2.double().to(dev)
+    if diag:
+        c = (a * b).sum(-1, keepdim=True)
+    else:
+        c = a @ b.transpose(-1, -2)
+    return _SphereMaternFromInner.apply(c, lengthscale, dim, float(nu), int(num_levels), 0).to(x1.device)
+
+
 def mandel_to_matrix(vec):
     """(..., d_vec) -> (..., d, d)."""
     lib = _lib.load()

@@ -135,6 +135,24 @@ int gabo_sphere_pairwise_cached(const double* x1, const double* x2, double* out,
 int gabo_sphere_from_inner(const double* inner, double* out, int64_t n, double beta, int flags, int order, gabo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Zonal series on the sphere: f(c) = sum_{k < n_coeff} coeff[k] P_k(c), c = <x, y>, with P_k the Gegenbauer polynomial of the sphere
+ * S^series_dim normalised to P_k(1) = 1:  P_0 = 1, P_1 = c, (k + d - 2) P_k = (2k + d - 3) c P_{k-1} - (k - 1) P_{k-2}, d = series_dim
+ * (d = 1: Chebyshev).  The Riemannian Matern and heat kernels (Borovitskiy et al. 2020) are such series with non-negative coefficients,
+ * positive definite for every lengthscale; their derivatives in c and in the lengthscale are series of the same kind (series_dim + 2 per
+ * derivative in c).  No clamp and no acos: f is a polynomial, finite with all its derivatives at c = +-1.  csrc/sphere_zonal.hip.
+ * coeff_host: n_coeff doubles in HOST memory, copied into the kernel arguments (no device allocation, no copy on the stream).
+ * 1 <= n_coeff <= 129 (GABO_ERR_ARG), series_dim >= 1 (GABO_ERR_DIM); checked on the host before anything is launched.
+ * gabo_sphere_zonal_from_inner: element-wise on n inner products.
+ * gabo_sphere_zonal_pairwise: the Gram matrix in one launch, shapes, strides, `diag` and GABO_SYMMETRIC (the only flag read; n1 == n2,
+ * result exactly symmetric) as in gabo_sphere_pairwise.  The bits of out_ij depend on row i of x1, row j of x2 and the series only.
+ */
+int gabo_sphere_zonal_from_inner(const double* inner, double* out, int64_t n, const double* coeff_host, int n_coeff, int series_dim,
+                                 gabo_stream_t stream);
+int gabo_sphere_zonal_pairwise(const double* x1, const double* x2, double* out, int64_t batch, int64_t n1, int64_t n2, int dim,
+                               int64_t x1_batch_stride, int64_t x2_batch_stride, const double* coeff_host, int n_coeff, int series_dim,
+                               int flags, int diag, gabo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Mandel vector <-> symmetric matrix.
  * Replaces  vector_to_symmetric_matrix_mandel_torch   Riemannian_utils/spd_utils_torch.py:159-194
  *           symmetric_matrix_to_vector_mandel_torch   Riemannian_utils/spd_utils_torch.py:197-226 (averages both triangles, :219)
