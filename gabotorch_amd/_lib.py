@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("GABO_HIP_LIB", os.path.join(_PKG, "libgabo_hip.so")) 
 GABO_OK = 0
 GABO_ERR_DIM, GABO_ERR_ARG, GABO_ERR_NOT_SPD, GABO_ERR_LAUNCH = -1, -2, -3, -4
 GABO_OUT_GAUSSIAN, GABO_OUT_DISTANCE, GABO_OUT_LAPLACE, GABO_SYMMETRIC = 0, 1, 2, 4
+GABO_OUT_ZONAL = 3                     # gabo_sphere_acq_params.flags only: the zonal series of the Riemannian Matern / heat kernels
 GABO_SPD_REG_MAX_DIM = 12
 GABO_SPD_BWD_REG_MAX_DIM = 16
 GABO_SPD_FWD_REG_MAX_DIM = 20
@@ -67,7 +68,7 @@ class SphereAcqParams(_c.Structure):
     _fields_ = [("train", _c.c_void_p), ("train_t", _c.c_void_p), ("alpha", _c.c_void_p), ("linv", _c.c_void_p), ("linv_t", _c.c_void_p),
                 ("n", _c.c_int64), ("dim", _c.c_int), ("beta", _c.c_double), ("flags", _c.c_int), ("mean", _c.c_double),
                 ("outputscale", _c.c_double), ("kxx", _c.c_double), ("best_f", _c.c_double), ("kind", _c.c_int), ("maximize", _c.c_int),
-                ("out_sign", _c.c_double)]
+                ("out_sign", _c.c_double), ("series", _c.c_void_p), ("series_levels", _c.c_int), ("series_dim", _c.c_int)]
 
 
 class SphereSweepConfig(_c.Structure):

@@ -11,12 +11,57 @@
 //                           constraints (sphere_constraints_utils_torch.py: coordinate bounds, geodesic ball) evaluated by the wave
 //   gabo_sphere_constraints_eval   values and Riemannian gradients of those constraints at R points, one launch
 // The scalar logic of the tCG iteration is tcg_step_core of spd_tcg_body.hpp (shared with the SPD kernels).
+// ZONAL (a template parameter from the strip loops up to the kernels; GABO_OUT_ZONAL picks it): the surrogate's kernel is a zonal series, the Riemannian
+// Matern / heat kernels of sphere_zonal.hip.  Only the strip loops of sph_acq_eval / sph_acq_hess differ; the geodesic instantiations are the
+// kernels this file had before it knew the series.
 #include "spd_tcg_body.hpp"
 #include "sphere_cons.hpp"
+#include "sphere_zonal_level.hpp"
 
 namespace gabo {
 
 using SphAcq = gabo_sphere_acq_params;
+
+// f(c), f'(c)[, f''(c)] of the zonal surrogate at one inner product: ONE pass over the levels advances the NS recurrences P^(d), P^(d+2)[, P^(d+4)]
+// (order o reads its levels at tab + o * L) in zonal_eval's form - ascending levels, t = c P_{k-1}, P_k = fma(B_k, t - P_{k-2}, t), f = fma(p_k, P_k, f),
+// two levels per trip so that P_{k-2} and P_{k-1} swap roles.  The table is the same for every lane: the levels come through the scalar cache
+// (constant address space).  A polynomial: no clamp, and nothing to mask at c = +-1.
+typedef const ZonalLevel __attribute__((address_space(4)))* ZonalTab;
+
+template <int NS>
+static __device__ __forceinline__ void sph_zonal_strip(const double* series, int L, double c, double (&f)[NS]) {
+    const ZonalTab tab = (ZonalTab)(uintptr_t)series;
+    double p0[NS], p1[NS];
+#pragma unroll
+    for (int o = 0; o < NS; ++o) {
+        const double a0 = tab[o * L].a, a1 = L > 1 ? tab[o * L + 1].a : 0.0;
+        p0[o] = 1.0;
+        p1[o] = c;
+        f[o] = __builtin_fma(a1, c, a0);
+    }
+    int k = 2;
+    for (; k + 1 < L; k += 2) {
+#pragma unroll
+        for (int o = 0; o < NS; ++o) {
+            const double ea = tab[o * L + k].a, eb = tab[o * L + k].rb, da = tab[o * L + k + 1].a, db = tab[o * L + k + 1].rb;
+            const double te = c * p1[o];
+            p0[o] = __builtin_fma(eb, te - p0[o], te);                    // P_k in the place of P_{k-2}
+            f[o] = __builtin_fma(ea, p0[o], f[o]);
+            const double to = c * p0[o];
+            p1[o] = __builtin_fma(db, to - p1[o], to);                    // P_{k+1} in the place of P_{k-1}
+            f[o] = __builtin_fma(da, p1[o], f[o]);
+        }
+    }
+    if (k < L) {
+#pragma unroll
+        for (int o = 0; o < NS; ++o) {
+            const double ea = tab[o * L + k].a, eb = tab[o * L + k].rb;
+            const double te = c * p1[o];
+            p0[o] = __builtin_fma(eb, te - p0[o], te);
+            f[o] = __builtin_fma(ea, p0[o], f[o]);
+        }
+    }
+}
 
 struct SphWs {
     double *g, *eta, *heta, *r, *delta, *x_fd, *eg_fd, *hd0, *x_prop, *eg_prop, *gc, *scal, *fc, *fcg_pe, *val_fd, *fx_prop, *rhoden;
@@ -79,6 +124,7 @@ static __device__ __forceinline__ double sph_col_dot(const double* __restrict__ 
 // value and (grad != nullptr) Euclidean gradient of out_sign * acquisition at x (dim doubles, global or LDS).  dyn: 3 n doubles of LDS.
 // P.linv == P.linv_t: the caller handed over the symmetric A = (outputscale K + noise I)^-1 (gabo_gp_factor's kinv) for both: one matrix-vector
 // product per evaluation instead of two (as the SPD evaluations, spd_acq_body.hpp).
+template <bool ZONAL>
 static __device__ __forceinline__ void sph_acq_eval(const double* __restrict__ x, const SphAcq& P, double* __restrict__ value_out,
                                     double* __restrict__ grad_out, double* dyn) {
     const int64_t n = P.n;
@@ -93,6 +139,13 @@ static __device__ __forceinline__ void sph_acq_eval(const double* __restrict__ x
     for (int64_t j = lane; j < n; j += 64) {
         double ip = 0.0;
         for (int k = 0; k < dim; ++k) ip = __builtin_fma(x[k], P.train_t[(int64_t)k * n + j], ip);
+        if constexpr (ZONAL) {
+            double f[2];
+            sph_zonal_strip<2>(P.series, P.series_levels, ip, f);
+            ks[j] = P.outputscale * f[0];
+            kd[j] = f[1];                                                       // (finite and not zero at c = +-1: no mask)
+            continue;
+        }
         const bool inside = ip >= lo && ip <= hi;
         const double c = ip < lo ? lo : (ip > hi ? hi : ip);
         const double th = acos(c);
@@ -152,6 +205,7 @@ static __device__ __forceinline__ void sph_acq_eval(const double* __restrict__ x
 //   G_j = A_mu alpha_j - 2 A_v q_j,  G'_j = (A_mumu mu' + A_muv var') alpha_j - 2 (A_muv mu' + A_vv var') q_j - 2 A_v qd_j
 //   egrad = sum_j G_j os f'(c_j) X_j,   ehess u = sum_j [G'_j os f'(c_j) + G_j os f''(c_j) s_j] X_j
 // dyn: 7 n doubles of LDS.
+template <bool ZONAL>
 static __device__ __forceinline__ void sph_acq_hess(const double* __restrict__ x, const double* __restrict__ u, const SphAcq& P,
                                     double* __restrict__ egrad_out, double* __restrict__ ehess_out, double* dyn) {
     const int64_t n = P.n;
@@ -172,6 +226,15 @@ static __device__ __forceinline__ void sph_acq_hess(const double* __restrict__ x
             const double xt = P.train_t[(int64_t)k * n + j];
             ip = __builtin_fma(x[k], xt, ip);
             su = __builtin_fma(u[k], xt, su);
+        }
+        if constexpr (ZONAL) {
+            double f[3];
+            sph_zonal_strip<3>(P.series, P.series_levels, ip, f);
+            ks[j] = P.outputscale * f[0];
+            f1[j] = P.outputscale * f[1];                                       // (finite and not zero at c = +-1: no mask)
+            f2[j] = P.outputscale * f[2];
+            sj[j] = su;
+            continue;
         }
         const bool inside = ip >= lo && ip <= hi;
         const double c = ip < lo ? lo : (ip > hi ? hi : ip);
@@ -302,6 +365,7 @@ static __device__ __forceinline__ double dotg(const double* a, const double* b, 
 
 // tCG + proposal + acquisition at the proposal for restart i.  lds: 6 dim doubles; dyn: 3 n doubles.  gc / fc == nullptr with C > 0: the
 // constraint gradients and values are already in the workspace (w.gc, w.fc: the single-launch solve evaluates them there, as tcg_begin).
+template <bool ZONAL>
 static __device__ __forceinline__ void sph_propose_body(const double* __restrict__ x, const double* __restrict__ g, double delta_tr,
                                         const double* __restrict__ gc, const double* __restrict__ fc, const SphAcq& P, const SphWs& w,
                                         int64_t i, int64_t R, int C, int neq, double delta_cons, double theta, double kappa,
@@ -373,7 +437,7 @@ static __device__ __forceinline__ void sph_propose_body(const double* __restrict
         }
         if (exact_hessian) {
             // Riemannian Hessian ([3P] Sphere.ehess2rhess): proj_x(ehess delta) - <x, egrad> delta
-            sph_acq_hess(xs, dl, P, egfd, xfd, dyn);               // egfd <- egrad(x), xfd <- ehess(x) delta
+            sph_acq_hess<ZONAL>(xs, dl, P, egfd, xfd, dyn);               // egfd <- egrad(x), xfd <- ehess(x) delta
             __syncthreads();
             const double xe = dotg(xs, egfd, dim);
             const double xh = dotg(xs, xfd, dim);
@@ -396,7 +460,7 @@ static __device__ __forceinline__ void sph_propose_body(const double* __restrict
         const double inv = 1.0 / __builtin_sqrt(wave_sum(yy));
         for (int e = threadIdx.x; e < dim; e += 64) { s0[e] *= inv; xfd[e] = s0[e]; }
         __syncthreads();
-        sph_acq_eval(s0, P, w.val_fd + i, egfd, dyn);
+        sph_acq_eval<ZONAL>(s0, P, w.val_fd + i, egfd, dyn);
         __syncthreads();
         // Hd = transp(x1 -> x, proj_x1(eg1)) / c - g / c
         const double a1 = dotg(s0, egfd, dim);
@@ -422,7 +486,7 @@ static __device__ __forceinline__ void sph_propose_body(const double* __restrict
     for (int e = threadIdx.x; e < dim; e += 64) { s0[e] *= inv; xp[e] = s0[e]; }
     if (threadIdx.x == 0) w.rhoden[i] = -ge - 0.5 * ehe;
     __syncthreads();
-    sph_acq_eval(s0, P, w.fx_prop + i, w.eg_prop + i * dim, dyn);
+    sph_acq_eval<ZONAL>(s0, P, w.fx_prop + i, w.eg_prop + i * dim, dyn);
 }
 
 static __device__ __forceinline__ bool sph_update_body(double* __restrict__ x, double* __restrict__ fx, double* __restrict__ g, double* __restrict__ ng,
@@ -522,6 +586,7 @@ __global__ __launch_bounds__(64) void sphere_constraints_kernel(const double* __
     sph_cons_eval(x + i * dim, dim, K, values + i * K.n, rgrads ? rgrads + i * dim : nullptr, R * dim);
 }
 
+template <bool ZONAL>
 __global__ __launch_bounds__(64) void sphere_acq_kernel(const double* __restrict__ x, SphAcq P, double* __restrict__ value,
                                                         double* __restrict__ grad, int64_t R) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
@@ -529,9 +594,10 @@ __global__ __launch_bounds__(64) void sphere_acq_kernel(const double* __restrict
     const int64_t i = blockIdx.x;
     for (int e = threadIdx.x; e < P.dim; e += 64) xs[e] = x[i * P.dim + e];
     __syncthreads();
-    sph_acq_eval(xs, P, value + i, grad ? grad + i * P.dim : nullptr, dyn);
+    sph_acq_eval<ZONAL>(xs, P, value + i, grad ? grad + i * P.dim : nullptr, dyn);
 }
 
+template <bool ZONAL>
 __global__ __launch_bounds__(64) void sphere_tr_propose_kernel(const double* __restrict__ x, const double* __restrict__ g,
                                                                const double* __restrict__ delta_tr, const uint8_t* __restrict__ active,
                                                                const double* __restrict__ gc, const double* __restrict__ fc, SphAcq P,
@@ -543,7 +609,7 @@ __global__ __launch_bounds__(64) void sphere_tr_propose_kernel(const double* __r
     if (i == 0 && threadIdx.x == 0) *any_active = 0;
     if (active[i] == 0) return;
     SphWs w = sph_layout(wsbase, R, P.dim, C);
-    sph_propose_body(x + i * P.dim, g + i * P.dim, delta_tr[i], gc, fc, P, w, i, R, C, neq, delta_cons, theta, kappa, mininner, maxinner,
+    sph_propose_body<ZONAL>(x + i * P.dim, g + i * P.dim, delta_tr[i], gc, fc, P, w, i, R, C, neq, delta_cons, theta, kappa, mininner, maxinner,
                      dyn + 7 * P.n, dyn, exact_hessian);
     __syncthreads();
     for (int e = threadIdx.x; e < P.dim; e += 64) x_prop[i * P.dim + e] = w.x_prop[i * P.dim + e];
@@ -580,7 +646,7 @@ static inline size_t sph_solve_lds(int64_t n, int dim, int64_t r, bool sym, int 
 
 // CONS: the built-in constraints K are evaluated by the wave - at the iterate (values and gradients into the workspace, kept while x does
 // not move) and, strict, at the proposal.  !CONS ignores K: the unconstrained instantiations are those the kernel had before it knew constraints.
-template <bool LAT, bool CONS>
+template <bool LAT, bool CONS, bool ZONAL>
 __global__ __launch_bounds__(64) void sphere_tr_solve_kernel(double* __restrict__ x, double* __restrict__ fx, double* __restrict__ g,
                                                              double* __restrict__ ng, double* __restrict__ delta_tr,
                                                              uint8_t* __restrict__ active, int64_t* __restrict__ iters, SphAcq P,
@@ -626,7 +692,7 @@ __global__ __launch_bounds__(64) void sphere_tr_solve_kernel(double* __restrict_
         if constexpr (CONS) {
             if (!x_unchanged) sph_cons_eval(x + i * P.dim, P.dim, K, w.fc + iw * C, w.gc + iw * P.dim, Rw * P.dim);
         }
-        sph_propose_body(x + i * P.dim, g + i * P.dim, delta_tr[i], nullptr, nullptr, Ps, w, iw, Rw, C, neq, delta_cons, theta, kappa, mininner,
+        sph_propose_body<ZONAL>(x + i * P.dim, g + i * P.dim, delta_tr[i], nullptr, nullptr, Ps, w, iw, Rw, C, neq, delta_cons, theta, kappa, mininner,
                          maxinner, dyn + 7 * P.n, dyn, exact_hessian, x_unchanged);
         __syncthreads();
         bool inval = false;
@@ -656,7 +722,9 @@ void tr_record_take(double** buffer, int64_t* capacity);      // spd_tr.hip
 static int sph_acq_ok(const SphAcq* a) {
     if (!a || a->n < 1 || a->n > 4096 || a->dim < 2 || a->dim > 512 || !a->train || !a->train_t || !a->alpha) return GABO_ERR_ARG;
     const int out = a->flags & GABO_OUT_MASK;
-    if ((a->flags & ~GABO_OUT_MASK) || (out != GABO_OUT_GAUSSIAN && out != GABO_OUT_LAPLACE)) return GABO_ERR_ARG;
+    if ((a->flags & ~GABO_OUT_MASK) || (out != GABO_OUT_GAUSSIAN && out != GABO_OUT_LAPLACE && out != GABO_OUT_ZONAL)) return GABO_ERR_ARG;
+    // the series of the zonal surrogate: a table of 3 x series_levels levels on the device, in the series dimension of this sphere
+    if (out == GABO_OUT_ZONAL && (!a->series || a->series_levels < 1 || a->series_levels > kZonalMaxCoeff || a->series_dim != a->dim - 1)) return GABO_ERR_ARG;
     if (a->kind != GABO_ACQ_EXPECTED_IMPROVEMENT && a->kind != GABO_ACQ_POSTERIOR_MEAN) return GABO_ERR_ARG;
     if (a->kind == GABO_ACQ_EXPECTED_IMPROVEMENT && (!a->linv || !a->linv_t)) return GABO_ERR_ARG;
     if ((size_t)(7 * a->n + 6 * a->dim) * sizeof(double) > 150 * 1024) return GABO_ERR_ARG;
@@ -675,7 +743,8 @@ int gabo_sphere_acq_eval(const double* x, const gabo_sphere_acq_params* acq, dou
     if (r == 0) return GABO_OK;
     if (!x || !value) return GABO_ERR_ARG;
     size_t lds = (size_t)(3 * acq->n + acq->dim) * sizeof(double);
-    hipLaunchKernelGGL(gabo::sphere_acq_kernel, dim3((unsigned)r), dim3(64), lds, (hipStream_t)stream, x, *acq, value, grad, r);
+    auto kernel = (acq->flags & GABO_OUT_MASK) == GABO_OUT_ZONAL ? gabo::sphere_acq_kernel<true> : gabo::sphere_acq_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)r), dim3(64), lds, (hipStream_t)stream, x, *acq, value, grad, r);
     return hipGetLastError() == hipSuccess ? GABO_OK : GABO_ERR_LAUNCH;
 }
 
@@ -704,7 +773,8 @@ int gabo_sphere_tr_propose(const double* x, const double* grad, const double* tr
         return GABO_ERR_ARG;
     if (workspace_bytes < gabo_sphere_tr_workspace_bytes(r, acq->dim, n_constraints)) return GABO_ERR_ARG;
     size_t lds = (size_t)(7 * acq->n + 6 * acq->dim) * sizeof(double);
-    hipLaunchKernelGGL(gabo::sphere_tr_propose_kernel, dim3((unsigned)r), dim3(64), lds, (hipStream_t)stream, x, grad, trust_radius, active,
+    auto kernel = (acq->flags & GABO_OUT_MASK) == GABO_OUT_ZONAL ? gabo::sphere_tr_propose_kernel<true> : gabo::sphere_tr_propose_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)r), dim3(64), lds, (hipStream_t)stream, x, grad, trust_radius, active,
                        cons_grads, cons_values, *acq, workspace, x_prop, r, n_constraints, n_equalities, delta_cons, theta, kappa,
                        mininner, maxinner, any_active, exact_hessian);
     return hipGetLastError() == hipSuccess ? GABO_OK : GABO_ERR_LAUNCH;
@@ -765,8 +835,11 @@ int gabo_sphere_tr_solve_constrained(double* x, double* fx, double* grad, double
     if (workspace_bytes < gabo_sphere_tr_workspace_bytes(r, acq->dim, n_constraints)) return GABO_ERR_ARG;
     bool lat = false;
     const size_t lds = gabo::sph_solve_lds(acq->n, acq->dim, r, acq->linv != nullptr && acq->linv == acq->linv_t, n_constraints, &lat);
-    auto kernel = n_constraints > 0 ? (lat ? gabo::sphere_tr_solve_kernel<true, true> : gabo::sphere_tr_solve_kernel<false, true>)
-                                    : (lat ? gabo::sphere_tr_solve_kernel<true, false> : gabo::sphere_tr_solve_kernel<false, false>);
+    auto geodesic = n_constraints > 0 ? (lat ? gabo::sphere_tr_solve_kernel<true, true, false> : gabo::sphere_tr_solve_kernel<false, true, false>)
+                                      : (lat ? gabo::sphere_tr_solve_kernel<true, false, false> : gabo::sphere_tr_solve_kernel<false, false, false>);
+    auto zonal = n_constraints > 0 ? (lat ? gabo::sphere_tr_solve_kernel<true, true, true> : gabo::sphere_tr_solve_kernel<false, true, true>)
+                                   : (lat ? gabo::sphere_tr_solve_kernel<true, false, true> : gabo::sphere_tr_solve_kernel<false, false, true>);
+    auto kernel = (acq->flags & GABO_OUT_MASK) == GABO_OUT_ZONAL ? zonal : geodesic;
     hipLaunchKernelGGL(kernel, dim3((unsigned)r), dim3(64), lds, (hipStream_t)stream, x, fx, grad, grad_norm, trust_radius, active, iters, *acq,
                        workspace, r, theta, kappa, mininner, maxinner, delta_bar, rho_prime, rho_regularization, mingradnorm, maxiter,
                        exact_hessian, rec, rec_cap, K);

@@ -16,15 +16,11 @@
 // ascending order from a zero accumulator, padded with 0 * 0, whatever the tile, n1, n2 or batch.
 #include "gabo_device.hpp"
 #include "gabo_mirror.hpp"
+#include "sphere_zonal_level.hpp"
 #include "../../include/gabo_hip.h"
 
 namespace gabo {
 
-constexpr int kZonalMaxCoeff = 129;
-
-struct ZonalLevel {
-    double a, rb;          // coeff_k, B_k
-};
 struct ZonalSeries {       // wave-uniform
     ZonalLevel lv[kZonalMaxCoeff + 3];      // (levels >= n: zeros; the loop requests up to three levels past the last one it uses)
     int n;

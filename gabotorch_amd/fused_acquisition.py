@@ -36,7 +36,7 @@ class FusedAcquisition:
         base, outputscale, mean, (linv, alpha), train_x = view if view is not None else _surrogate_view(acq.model)
         self.family, self.mode, self.beta, self.matrix_input = family, mode, beta, matrix_input
         self.flavour = flavour          # SPD kernels: "ai" affine-invariant, "le" log-Euclidean, "frob" Frobenius
-        self.zonal = None               # sphere Matern / heat kernel: the host's series of f and f' (`beta` is the lengthscale, `mode` unused)
+        self.zonal = None               # sphere Matern / heat kernel: the host's series of f and f' (`beta` is the lengthscale, `mode` GABO_OUT_ZONAL under `series_launch`)
         self.kind = _lib.GABO_ACQ_EXPECTED_IMPROVEMENT if isinstance(acq, models.ExpectedImprovement) else _lib.GABO_ACQ_POSTERIOR_MEAN
         self.maximize = bool(acq.maximize)
         self.best_f = float(getattr(acq, "best_f", 0.0))
@@ -58,6 +58,7 @@ class FusedAcquisition:
         self.train = on(train_x)
         # d <= 12: value + gradient in ONE launch per evaluation (csrc/spd_acq.hip); the training side is factored once here
         self.single_launch = False
+        self.series_launch, self.series, self.series_levels, self.series_dim = False, None, 0, 0
         if family == "spd" and flavour == "ai":
             d_spd = ops._mandel_dim(self.train.shape[-1])
             self.single_launch = (d_spd <= _lib.GABO_SPD_REG_MAX_DIM
@@ -67,11 +68,18 @@ class FusedAcquisition:
             n_tr, dim_tr = self.train.shape
             self.single_launch = (7 * n_tr + 6 * dim_tr) * 8 <= 150 * 1024 and n_tr <= 4096 and 2 <= dim_tr <= 512
             if zonal is not None:
-                # no single-launch evaluator for the series kernels (csrc/sphere_tr.hip knows the geodesic kernels only): the lock-step plan
+                # `single_launch` keeps its meaning, the closed-form geodesic evaluators; the series kernels run the ZONAL instantiations of the
+                # same launches (csrc/sphere_tr.hip, GABO_OUT_ZONAL) under the same shape limits: `series_launch`, and `one_launch` for both
                 nu, num_levels = zonal
-                self.single_launch = False
+                self.series_launch, self.single_launch = self.single_launch, False
                 self.zonal = tuple(ops.sphere_matern_coefficients(dim_tr, beta, nu, num_levels, order) for order in (0, 1))
-            self.train_t = self.train.t().contiguous() if self.single_launch else None
+                if self.series_launch:
+                    # f, f' and f'' as (coefficient, B_k) levels, built once on the host and copied to the device (too large for kernel arguments)
+                    table = ops.sphere_zonal_table(self.zonal[0][0], dim_tr - 1)
+                    self.series_levels, self.series_dim = int(table.shape[1]), dim_tr - 1
+                    self.series = torch.from_numpy(table).to(device)
+                    self.mode = _lib.GABO_OUT_ZONAL
+            self.train_t = self.train.t().contiguous() if self.one_launch else None
         self.metric = {"ai": _lib.GABO_METRIC_AFFINE_INVARIANT, "le": _lib.GABO_METRIC_LOG_EUCLIDEAN, "frob": _lib.GABO_METRIC_FROBENIUS}[flavour]
         self.train_factors = None
         if self.single_launch and family == "spd":
@@ -99,6 +107,12 @@ class FusedAcquisition:
             # <x, x> is clamped to 1 - 1e-15 (sphere_utils_torch.py:53): d(x, x) = acos(1 - 1e-15)
             t0 = math.acos(1.0 - 1e-15)
             self.kxx = math.exp(-beta * (t0 * t0 if mode == _lib.GABO_OUT_GAUSSIAN else t0))
+
+    @property
+    def one_launch(self):
+        """value and gradient in one launch per evaluation, and with it the device-resident trust-region plans: the closed-form evaluators
+        (`single_launch`) or, on the sphere, the series evaluators of the Matern / heat kernels (`series_launch`)"""
+        return self.single_launch or self.series_launch
 
     @staticmethod
     def build(acq, post_processing, device):
@@ -200,7 +214,8 @@ class FusedAcquisition:
         la, lb = (self.kinv.data_ptr(), self.kinv.data_ptr()) if self.kinv is not None else (self.linv.data_ptr(), self.linv_t.data_ptr())
         return _lib.SphereAcqParams(self.train.data_ptr(), self.train_t.data_ptr(), self.alpha.data_ptr(), la,
                                     lb, self.train.shape[0], self.train.shape[1], self.beta, int(self.mode), self.mean,
-                                    self.outputscale, self.kxx, self.best_f, int(self.kind), 1 if self.maximize else 0, -1.0)
+                                    self.outputscale, self.kxx, self.best_f, int(self.kind), 1 if self.maximize else 0, -1.0,
+                                    self.series.data_ptr() if self.series_launch else None, self.series_levels, self.series_dim)
 
     def acq_params(self):
         """The surrogate as the gabo_spd_acq_params struct of the C ABI (single-launch path only)."""
@@ -217,7 +232,7 @@ class FusedAcquisition:
                                 active_ptr=active_ptr, out=out)
 
     def cost(self, x):
-        if self.single_launch and self.family == "sphere":
+        if self.one_launch and self.family == "sphere":
             return ops.sphere_acq_eval(x.detach(), self.sphere_acq_params(), need_grad=False)[0]
         if self.single_launch:
             return self._single(ops.matrix_to_mandel(x.detach()) if self.matrix_input else x.detach(), False)[0]
@@ -227,7 +242,7 @@ class FusedAcquisition:
         return val
 
     def cost_egrad(self, x):
-        if self.single_launch and self.family == "sphere":
+        if self.one_launch and self.family == "sphere":
             return ops.sphere_acq_eval(x.detach(), self.sphere_acq_params(), need_grad=True)
         if self.single_launch:
             val, g = self._single(ops.matrix_to_mandel(x.detach()) if self.matrix_input else x.detach(), True)

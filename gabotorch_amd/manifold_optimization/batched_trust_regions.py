@@ -622,7 +622,8 @@ class BatchedTrustRegions:
         sphere = fused.family == "sphere"
         one_launch = False
         builtins, lift = None, None
-        fused_kernels = getattr(fused, "single_launch", False) and getattr(problem, "device_iteration", True) and not self.use_rand
+        fused_kernels = (getattr(fused, "one_launch" if sphere else "single_launch", False) and getattr(problem, "device_iteration", True)
+                         and not self.use_rand)
         # (the library says which of its iteration kernels exist for this surrogate: e.g. no propose / update pair for the log-Euclidean
         # surrogate at d = 8, csrc/spd_tr_le_hi.hip, and no generic-workspace single launch for it at d = 7, 8, csrc/spd_tr_body.hpp)
         propose_ok = bool(fused_kernels and (sphere or _library().gabo_spd_tr_propose_supported(int(fused.mode) | int(fused.metric), d)))
@@ -844,7 +845,7 @@ class BatchedTrustRegions:
                 or not getattr(problem, "device_tcg", True) or ncons > 8 or x.dtype != torch.float64):
             return False
         if fused.family == "sphere":       # csrc/sphere_tr.hip: propose / update / solve kernels, FD or exact (closed-form) Hessian
-            return (isinstance(problem.manifold, Sphere) and fused.single_launch and x.dim() == 2
+            return (isinstance(problem.manifold, Sphere) and fused.one_launch and x.dim() == 2
                     and getattr(problem, "device_iteration", True))
         return (problem.approx_hessian and fused.family == "spd" and fused.matrix_input
                 and isinstance(problem.manifold, PositiveDefinite) and x.shape[-1] <= 32)

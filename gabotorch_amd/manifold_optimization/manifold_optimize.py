@@ -475,7 +475,7 @@ def _native_sweep_plan(acq_function, manifold, solver, q, num_restarts, raw_samp
             if group is None:
                 return None
         fused = FusedAcquisition.build(acq_function, None, dev)
-        if fused is None or not (fused.family == "sphere" and fused.single_launch):
+        if fused is None or not (fused.family == "sphere" and fused.one_launch):
             return None
         return {"fused": fused, "device": dev, "manifold": manifold, "builtins": [], "device_rand": False, "sphere": True,
                 "exact_hessian": not approx_hessian, "sphere_group": group, "n_equalities": len(eqs)}

@@ -664,6 +664,26 @@ def sphere_matern_coefficients(dim, lengthscale, nu, num_levels, order=0, wrt_le
     return np.ascontiguousarray(p, dtype=np.float64), series_dim
 
 
+def sphere_zonal_table(coeff, series_dim):
+    """The series f = sum_k coeff[k] P_k^(series_dim) with its first and second derivative in c as the table gabo_sphere_acq_params.series points
+    to: numpy (3, len(coeff), 2) of (coefficient, B_k) pairs, order o in series dimension series_dim + 2 o (B_k = (k - 1) / (k + d - 2), B_0 = B_1 = 0),
+    the shorter derivative series zero-padded.  The derivative coefficients are those of sphere_matern_coefficients(order=1, 2)."""
+    import numpy as np
+    p = np.ascontiguousarray(coeff, dtype=np.float64).reshape(-1)
+    L, sd = int(p.size), int(series_dim)
+    if not 1 <= L <= SPHERE_ZONAL_MAX_LEVELS + 1:
+        raise ValueError(f"sphere_zonal_table: {L} levels outside 1 ... {SPHERE_ZONAL_MAX_LEVELS + 1}")
+    if sd < 1:
+        raise ValueError(f"sphere_zonal_table: series dimension {series_dim} must be at least 1")
+    table = np.zeros((3, L, 2))
+    k = np.arange(2, L, dtype=np.float64)
+    for order in range(3):
+        table[order, :min(p.size, L), 0] = p[:L]
+        table[order, 2:, 1] = (k - 1.0) / (k + float(sd) - 2.0)       # (one IEEE division each, as zonal_series of csrc/sphere_zonal.hip)
+        p, sd = _zonal_derivative(p, sd)
+    return table
+
+
 def _zonal_coeff(coeff):
     import numpy as np
     a = np.ascontiguousarray(coeff, dtype=np.float64).reshape(-1)

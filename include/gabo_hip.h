@@ -34,6 +34,7 @@ typedef void* gabo_stream_t; /* hipStream_t */
 #define GABO_OUT_GAUSSIAN 0     /* out = exp(-beta * d^2)            kernels_spd.py:96-98, kernels_sphere.py:91-93 */
 #define GABO_OUT_DISTANCE 1     /* out = d                           spd_utils_torch.py:120, sphere_utils_torch.py:55 */
 #define GABO_OUT_LAPLACE 2      /* out = exp(-beta * d)              kernels_spd.py:185, kernels_sphere.py:133 */
+#define GABO_OUT_ZONAL 3        /* out = sum_k p_k P_k(<x, y>), a zonal series (gabo_sphere_acq_params.series): the sphere acquisition entries only */
 #define GABO_OUT_MASK 3
 #define GABO_SYMMETRIC 4        /* x1 and x2 are the same set (n1 == n2): evaluate i <= j only and mirror */
 /* distance used by the fused acquisition kernels (gabo_spd_acq_params.flags, OR-ed with GABO_OUT_GAUSSIAN / GABO_OUT_LAPLACE) */
@@ -716,10 +717,18 @@ typedef struct {
     int64_t n;
     int dim;
     double beta;
-    int flags;               /* GABO_OUT_GAUSSIAN / GABO_OUT_LAPLACE */
+    int flags;               /* GABO_OUT_GAUSSIAN / GABO_OUT_LAPLACE / GABO_OUT_ZONAL */
     double mean, outputscale, kxx, best_f;
     int kind, maximize;
     double out_sign;
+    /* GABO_OUT_ZONAL (the Riemannian Matern / heat kernels, SphereRiemannianMaternKernel): the kernel is the zonal series f(c) = sum_k p_k P_k(c),
+     * c = <x, X_j>, a polynomial - no clamp, no acos, f' and f'' finite at c = +-1.  `series`: device memory, 3 x series_levels pairs
+     * (coefficient, B_k) - the levels of f, then of f', then of f'' (order o in series dimension series_dim + 2 o, B_k = (k - 1) / (k + d - 2),
+     * B_0 = B_1 = 0; ops.sphere_matern_coefficients with order = o), each order zero-padded to series_levels.  1 <= series_levels <= 129,
+     * series_dim == dim - 1; beta is ignored, kxx is the caller's f(1).  Ignored (may be NULL / 0) with the other flags. */
+    const double* series;
+    int series_levels;
+    int series_dim;
 } gabo_sphere_acq_params;
 int gabo_sphere_acq_eval(const double* x, const gabo_sphere_acq_params* acq, double* value, double* grad, int64_t r,
                          gabo_stream_t stream);
