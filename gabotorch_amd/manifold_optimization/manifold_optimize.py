@@ -17,6 +17,7 @@ import torch
 from ..models import (BadInitialCandidatesWarning, get_best_candidates, initialize_q_batch, initialize_q_batch_nonneg,
                       is_nonnegative)
 from ..fused_acquisition import FusedAcquisition
+from .._status import _not_spd_message
 from .batched_trust_regions import BatchedProblem, BatchedTrustRegions, default_limits
 
 
@@ -570,10 +571,10 @@ class _RowsState:
         """after the stream has drained: did a launch of call `which` (0 score, 1 solve) report a non-SPD matrix?  Host memory only."""
         e = self.err[2 * which:2 * which + 2]
         if e[0] != 0:
-            idx = int(e[1])
+            st = [int(e[0]), int(e[1])]
             e[:] = 0
             self.status[which].zero_()
-            raise RuntimeError(f"{what}: input matrix #{idx} is not positive definite (Cholesky pivot <= 0)")
+            raise RuntimeError(_not_spd_message(what)(st))
 
 
 def _rows_state(lib, dev, stream, n_train, d, max_rows, restarts, n_constraints):
@@ -599,7 +600,7 @@ def _native_sweep(plan, acq_function, solver, num_restarts, raw_samples, options
     import ctypes
     import time
 
-    from .. import _lib, ops
+    from .. import _lib, _status, ops
     if plan.get("sphere"):
         return _native_sweep_sphere(plan, acq_function, solver, num_restarts, raw_samples, options)
     lib = _lib.load()
@@ -622,7 +623,7 @@ def _native_sweep(plan, acq_function, solver, num_restarts, raw_samples, options
     cfg.mingradnorm, cfg.maxiter = float(solver.mingradnorm), int(solver.maxiter)
     nonneg, eta, alpha = _selection(acq_function, options)
     cfg_ref = ctypes.byref(cfg)
-    checking = ops._check_errors is not False
+    checking = _status.error_checking() is not False
     # the selection on the device (gabo_spd_sweep_select_rows) when it is botorch's non-negative heuristic on a table the kernel takes
     on_device = bool(options.get("device_selection", True)) and nonneg and bool(lib.gabo_spd_sweep_select_supported(raw_samples, R))
     r_loc, r_per = len(range(rank, R, world)), (R + world - 1) // world

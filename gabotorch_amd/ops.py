@@ -6,31 +6,9 @@ tensors); without a GPU every call raises - there is no CPU implementation in th
 """
 import torch
 
-from . import _lib
-
-_check_errors = "deferred"
-
-
-def set_error_checking(flag):
-    """How device-side data errors (a non-SPD input matrix, a NaN entry) reach the caller.  The reference raises from torch.cholesky at the call
-    (spd_utils_torch.py:87); a launch is asynchronous, so raising AT the call costs a stream synchronisation per call.
-      "deferred" (default): every launch gets a status word of its own; the words are read back - ONE copy for all pending launches of a stream -
-                 at the next synchronisation point: check_deferred(), which the acquisition sweep, the GP posterior and the solvers call where
-                 they wait for the device anyway, or when 63 launches are pending on one stream.  The RuntimeError names the launch that failed.
-      True / "sync": read back after every call (one stream synchronisation per call): the reference's behaviour to the statement.
-      False:     never read.
-    Returns the previous setting."""
-    global _check_errors
-    prev = _check_errors
-    if flag == "sync":
-        flag = True
-    if flag not in (True, False, "deferred"):
-        raise ValueError("set_error_checking: True / 'sync', 'deferred' or False")
-    if prev is False and flag is not False:
-        for ring in _status_rings.values():       # (nobody looked at the words while checking was off: start from clean ones)
-            ring.reset()
-    _check_errors = flag
-    return prev
+from . import _lib, _status
+from ._status import (_check_launch, _deferred, _not_spd_message, _raise_if_not_spd, _status_rings, _status_word,     # noqa: F401
+                      check_deferred, check_prefetched, prefetch_deferred, set_error_checking)      # (device status words: ops.* as before)
 
 
 def _device_for(*tensors):
@@ -103,89 +81,14 @@ def _require(dev, **tensors):
                             f"{'' if not torch.is_tensor(t) or t.is_contiguous() else ' (not contiguous)'}")
 
 
-class _StatusRing:
-    """The status words (two int32: error code, index of the offender) of the launches on ONE stream of one device: a ring of `N` words in
-    device memory, zeroed once - the kernels only ever write a word on an error, so no fill launch in front of a call (4 us of GPU time next to a
-    6 us projection, profiles/r03_config5_kernel_stats.csv) - each launch taking the next word.  `pending` holds (slot, message, on_fail) of the
-    launches nobody has checked yet; check() waits for the stream, reads the whole ring in one copy, forgets the launches that succeeded and raises
-    for the first that did not (clearing its word, calling its on_fail first)."""
-    N = 64
-
-    def __init__(self, dev, stream):
-        self.buf = torch.zeros(self.N, 2, dtype=torch.int32, device=dev)
-        self.stream = stream
-        self.next = 0
-        self.pending = []
-
-    def take(self):
-        k = self.next = self.next % (self.N - 1) + 1          # slots 1 ... N - 1 (slot 0: the word of launches nobody checks)
-        w = self.buf[k]
-        w._gabo_slot = (self, k)
-        return w
-
-    def reset(self):
-        with torch.cuda.stream(self.stream):
-            self.buf.zero_()
-        self.pending.clear()
-
-    def prefetch(self):
-        """Enqueue, behind everything on the ring's stream so far, a copy of the ring into page-locked host memory; -> how many pending launches
-        it covers.  For a caller that is about to wait for the stream anyway: evaluate() afterwards costs no device access."""
-        if getattr(self, "host", None) is None:
-            self.host = torch.zeros(self.N, 2, dtype=torch.int32).pin_memory()
-        if _stream_ptr(self.buf.device) == self.stream.cuda_stream:
-            self.host.copy_(self.buf, non_blocking=True)
-        else:
-            with torch.cuda.stream(self.stream):
-                self.host.copy_(self.buf, non_blocking=True)
-        return len(self.pending)
-
-    def check(self):
-        if not self.pending:
-            return
-        with torch.cuda.stream(self.stream):
-            vals = self.buf.cpu()              # (waits for everything enqueued on the ring's stream)
-        self.evaluate(vals.tolist(), len(self.pending))
-
-    def evaluate(self, vals, count):
-        """the first `count` pending launches against a host copy of the ring taken after they had completed"""
-        for _ in range(min(count, len(self.pending))):
-            k, message, on_fail = self.pending.pop(0)
-            st = vals[k]
-            if st[0] != 0:
-                st = [int(st[0]), int(st[1])]
-                with torch.cuda.stream(self.stream):
-                    self.buf[k].zero_()
-                if on_fail is not None:
-                    on_fail()
-                raise RuntimeError(message(st) if callable(message) else message)
-
-
-_status_rings = {}
-
-
-def _status_word(dev, force=False):
-    """A status word for the launch about to be enqueued on the current stream of `dev` (a view of that stream's ring: _StatusRing).
-    force: a word that is registered and read even while error checking is off (the GP's Cholesky: see gp_factor)."""
-    key = (dev.index, _stream_ptr(dev))
-    ring = _status_rings.get(key)
-    if ring is None:
-        ring = _status_rings[key] = _StatusRing(dev, torch.cuda.current_stream(dev))
-    if _check_errors is False and not force:
-        return ring.buf[0]          # (never read while checking is off; set_error_checking clears the ring when it comes back on)
-    if len(ring.pending) >= ring.N - 2:
-        ring.check()
-    return ring.take()
-
-
 def _out(t, out_device):
     """The result on the caller's device.  A caller that handed CPU tensors gets a CPU tensor back - a device -> host copy that waits for the
     stream anyway: the natural point to look at the status words of the launches behind it (deferred error checking: one more small copy)."""
     if t.device == out_device:
         return t
     r = t.to(out_device)
-    if _check_errors == "deferred" and out_device.type == "cpu":
-        check_deferred()
+    if _status.error_checking() == "deferred" and out_device.type == "cpu":
+        _status.check_deferred()
     return r
 
 
@@ -194,81 +97,6 @@ def _mandel_dim(dv):
     if d * (d + 1) // 2 != dv:
         raise RuntimeError(f"last dimension {dv} is not d(d+1)/2")
     return d
-
-
-def _not_spd_message(what):
-    return lambda st: f"{what}: input matrix #{st[1]} is not positive definite (Cholesky pivot <= 0)"
-
-
-def _raise_if_not_spd(status, what, message=None, on_fail=None, force=False):
-    """Called after the launch that was handed `status`: registers the launch for the next check (deferred), or reads the word now (sync).
-    message: the RuntimeError's text, or a callable of the two status ints; on_fail: called before raising (e.g. to drop a cache the failed launch
-    was meant to fill)."""
-    if _check_errors is False and not force:
-        return
-    message = message or _not_spd_message(what)
-    slot = getattr(status, "_gabo_slot", None)
-    if slot is not None:
-        ring, k = slot
-        ring.pending.append((k, message, on_fail))
-        if _check_errors is True:
-            ring.check()
-        return
-    # a word of the caller's own (fixed address: captured in a hipGraph, or owned by a solver object)
-    if _check_errors is True:
-        st = status.tolist()
-        if st[0] != 0:
-            status.zero_()
-            if on_fail is not None:
-                on_fail()
-            raise RuntimeError(message(st) if callable(message) else message)
-    else:
-        _deferred.append((status, message, on_fail))
-        if len(_deferred) > 32:
-            check_deferred()
-
-
-def _check_launch(rc, status, what, on_fail=None):
-    """return code first, then the device status word.  A launch refused by its return code never ran: its word is not registered."""
-    try:
-        _lib.check(rc, what)
-    except Exception:
-        if on_fail is not None:
-            on_fail()
-        raise
-    _raise_if_not_spd(status, what, on_fail=on_fail)
-
-
-_deferred = []
-
-
-def prefetch_deferred():
-    """For a caller that is about to wait for its stream anyway (the acquisition sweep before its scoring call returns): enqueue the read-back of
-    every status ring that has unchecked launches and return a token for check_prefetched - which then needs no device access at all."""
-    return [(ring, ring.prefetch()) for ring in _status_rings.values() if ring.pending]
-
-
-def check_prefetched(token):
-    """check_deferred for the launches covered by prefetch_deferred's token; ONLY after the streams those copies were enqueued on have been
-    waited for (the data is read from host memory as it is)."""
-    for ring, count in token:
-        ring.evaluate(ring.host.numpy(), count)
-
-
-def check_deferred():
-    """Reads the status words of every launch that has not been checked yet - one copy per stream that has any - and raises for the first failure,
-    naming the launch.  Called at the natural host synchronisation points of a sweep (after the raw samples' scores have reached the host, after a
-    solve, before a posterior); free when nothing is pending.  The launches that were still queued behind a failed one stay queued."""
-    for ring in list(_status_rings.values()):
-        ring.check()
-    while _deferred:
-        status, message, on_fail = _deferred.pop(0)
-        st = status.tolist()
-        if st[0] != 0:
-            status.zero_()
-            if on_fail is not None:
-                on_fail()
-            raise RuntimeError(message(st) if callable(message) else message)
 
 
 def spd_ai_pairwise(x1, x2, beta=1.0, mode=_lib.GABO_OUT_GAUSSIAN, symmetric=False, return_dist=False):

@@ -167,6 +167,36 @@ def test_deferred_errors_on_two_streams_are_attributed_to_their_launches():
     assert any("gabo_spd_acq_prepare_train: input matrix #7" in m for m in seen), seen
 
 
+def test_switching_error_checking_off_and_on_keeps_a_pending_failure():
+    """What the hipGraph plan of BatchedTrustRegions does around its capture: a failed GP factor queued in front of it is still reported."""
+    rng = np.random.default_rng(3)
+    _, good = _bad_and_good(rng)
+    y = torch.tensor(rng.standard_normal(12), device=DEV)
+    k = ops.spd_ai_pairwise(good, good, beta=0.7) - 2.0 * torch.eye(12, dtype=torch.float64, device=DEV)        # K - 2 I: indefinite
+    ops.check_deferred()
+    ops.gp_factor(k, y, 1.0, 0.0, 0.0, defer_check=True)
+    assert ops.set_error_checking(False) == "deferred"
+    assert ops.set_error_checking("deferred") is False
+    with pytest.raises(RuntimeError, match="not positive definite"):
+        ops.check_deferred()
+    ops.check_deferred()
+
+
+def test_a_prefetch_token_overtaken_by_a_check_loses_no_later_error():
+    """The token names its launches: checked by somebody else in the meantime, it has nothing left to say about the launches behind them."""
+    bad, good = _bad_and_good(np.random.default_rng(0))
+    ops.spd_ai_pairwise(good, good, beta=0.7)
+    token = ops.prefetch_deferred()
+    torch.cuda.synchronize()
+    ops.check_deferred()
+    ops.spd_ai_pairwise(bad, good, beta=0.7)
+    torch.cuda.synchronize()
+    ops.check_prefetched(token)                                         # silent: its one launch has been checked already
+    with pytest.raises(RuntimeError, match=r"gabo_spd_ai_pairwise: input matrix #5 is not positive definite"):
+        ops.check_deferred()
+    ops.check_deferred()
+
+
 def test_a_failed_factorisation_drops_the_models_cache():
     """models.ExactGP published its prediction cache before the Cholesky status was known; a caller that caught the RuntimeError and asked
     again got values computed from uninitialised memory.  The cache is now dropped before the error is raised, so the second request fails the same way."""
