@@ -3,7 +3,10 @@
 SphereGaussianKernel with the beta_min ladder, stock trust regions with EXACT Hessian-vector products (double backward
 through the sphere kernel), EI, 5 restarts / 100 raw samples.
 
-    python examples/gabo_sphere.py [--dim 3] [--iters 25]
+    python examples/gabo_sphere.py [--dim 3] [--iters 25] [--kernel gaussian|matern]
+
+--kernel matern: the Riemannian Matern kernel (nu = 5/2, positive definite for every lengthscale: no beta_min ladder) under the same priors; the
+surrogate fit is then one gabo_gp_mll_series launch per evaluation and the acquisition sweep the native one.
 """
 import argparse
 import os
@@ -16,14 +19,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gabotorch_amd import manifolds, models                                                           # noqa: E402
 from gabotorch_amd._compat import ScaleKernel                                                          # noqa: E402
 from gabotorch_amd.BO_test_functions.test_functions import ackley_function_sphere                      # noqa: E402
-from gabotorch_amd.kernel_utils.kernels_sphere import SphereGaussianKernel                             # noqa: E402
+from gabotorch_amd.kernel_utils.kernels_sphere import SphereGaussianKernel, SphereRiemannianMaternKernel      # noqa: E402
 from gabotorch_amd.manifold_optimization.batched_trust_regions import BatchedTrustRegions              # noqa: E402
 from gabotorch_amd.manifold_optimization.manifold_optimize import joint_optimize_manifold              # noqa: E402
 
 BETA_MIN = {3: 6.5, 4: 2.0, 5: 1.2, 11: 0.6, 21: 0.35, 51: 0.21, 101: 0.21}     # examples/gabo_sphere.py:115-128
 
 
-def run(dim=3, iters=25, restarts=5, raw=100, seed=1234, device="cuda:0", verbose=True):
+def run(dim=3, iters=25, restarts=5, raw=100, seed=1234, device="cuda:0", verbose=True, kernel="gaussian"):
     np.random.seed(seed)
     torch.manual_seed(seed)
     man = manifolds.Sphere(dim)
@@ -33,7 +36,8 @@ def run(dim=3, iters=25, restarts=5, raw=100, seed=1234, device="cuda:0", verbos
     solver = BatchedTrustRegions()                              # pyman_solvers.TrustRegions() (:151)
     best = [float(y_data.min())]
     for it in range(iters):
-        kern = ScaleKernel(SphereGaussianKernel(beta_min=BETA_MIN.get(dim, 0.6)), outputscale_prior=models.GammaPrior(2.0, 0.15))
+        base = SphereRiemannianMaternKernel() if kernel == "matern" else SphereGaussianKernel(beta_min=BETA_MIN.get(dim, 0.6))
+        kern = ScaleKernel(base, outputscale_prior=models.GammaPrior(2.0, 0.15))
         gp = models.SingleTaskGP(x_data, y_data, kern, noise_prior=models.GammaPrior(1.1, 0.05))
         models.fit_gpytorch_model(gp)
         acq = models.ExpectedImprovement(gp, best_f=float(y_data.min()), maximize=False)
@@ -52,5 +56,6 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--dim", type=int, default=3)
     ap.add_argument("--iters", type=int, default=25)
+    ap.add_argument("--kernel", choices=("gaussian", "matern"), default="gaussian")
     a = ap.parse_args()
-    run(a.dim, a.iters)
+    run(a.dim, a.iters, kernel=a.kernel)

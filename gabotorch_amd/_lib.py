@@ -124,6 +124,7 @@ SIGNATURES = {
     "gabo_gp_acquisition": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _D, _D, _D, _D, _I, _I, _D, _P]),
     "gabo_gp_mll": (_I, [_P, _P, _I64, _D, _D, _D, _D, _P, _P]),
     "gabo_gp_mll_gram": (_I, [_P, _P, _I64, _D, _D, _D, _P, _P, _P]),
+    "gabo_gp_mll_series": (_I, [_P, _P, _I64, _P, _P, _I, _I, _D, _D, _D, _P, _P]),
     "gabo_gp_factor": (_I, [_P, _P, _I64, _D, _D, _D, _P, _P, _P, _P, _P, _P]),
     "gabo_gp_mll_large_workspace_bytes": (_SZ, [_I64]),
     "gabo_gp_mll_large": (_I, [_P, _P, _I64, _D, _D, _D, _D, _I, _P, _P, _P, _SZ, _P]),

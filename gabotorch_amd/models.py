@@ -495,7 +495,7 @@ class SingleTaskGP(torch.nn.Module):
             self.train_y = targets.double().reshape(-1)
         self.invalidate()
 
-    # ---- fast surrogate fit: the distances are evaluated once, each evaluation is one gabo_gp_mll launch ------------------
+    # ---- fast surrogate fit: the distances (inner products) are evaluated once, each evaluation is one gabo_gp_mll (_series) launch ----
     def _stationary_form(self):
         """(E, theta_fn, outputscale_fn) when the covariance is [ScaleKernel of] one of the path's plain kernels, all of which
         are exp(-theta * E) with E = d^2 or d fixed during a fit; None for anything else (nested kernels carry extra
@@ -526,21 +526,64 @@ class SingleTaskGP(torch.nn.Module):
         e = kernel_parameters.exponent_matrix(base, x)[0]
         return e, theta_fn, os_fn
 
+    def _series_form(self):
+        """(C, kappa -> (p, dp / dkappa, series_dim), outputscale_fn) when the covariance is [ScaleKernel of] SphereRiemannianMaternKernel:
+        a zonal series of the inner products C = X X^T, which are fixed during a fit while the coefficients move with the lengthscale kappa
+        (ops.gp_mll_series); None for anything else, a batched lengthscale or more than GABO_GP_MLL_LARGE_MAX_N points.  C is the product
+        the differentiable route of ops.sphere_matern_kernel forms, so the value agrees with marginal_log_likelihood() to rounding."""
+        from . import _lib, ops
+        from .kernel_utils.kernels_sphere import SphereRiemannianMaternKernel
+        cm = self.covar_module
+        base = getattr(cm, "base_kernel", None)
+        if base is None:
+            base, os_fn = cm, (lambda: torch.ones((), dtype=torch.float64))
+        elif type(cm).__name__ == "ScaleKernel" and cm.raw_outputscale.numel() == 1:
+            os_fn = lambda: cm.outputscale.double().reshape(())                                # noqa: E731
+        else:
+            return None
+        x = self.train_x
+        if type(base) is not SphereRiemannianMaternKernel or x.dim() != 2 or not 1 <= x.shape[0] <= _lib.GABO_GP_MLL_LARGE_MAX_N:
+            return None
+        if base.raw_lengthscale.numel() != 1:
+            return None
+        with torch.no_grad():
+            xd = x.double().to(ops._device_for(x))
+            c = (xd @ xd.transpose(-1, -2)).contiguous()
+        dim, nu, levels = x.shape[-1], base.nu, base.num_levels
+        return c, (lambda kappa: ops.sphere_matern_coefficients_and_derivative(dim, kappa, nu, levels)), os_fn
+
+    def _fast_evaluator(self):
+        """(launch(parameter, outputscale, noise, mean) -> the six numbers of ops.gp_mll, parameter_fn, outputscale_fn, series?) on the matrix
+        that is fixed during a fit: the exponent matrix of a plain kernel (parameter theta), else the inner products of the sphere Matern
+        kernel (parameter: the lengthscale kappa itself); None when the model has neither form."""
+        from . import ops
+        form = self._stationary_form()
+        if form is not None:
+            e, theta_fn, os_fn = form
+            y = self.train_y.to(e.device).contiguous()
+            return (lambda theta, os_, noise, mean: ops.gp_mll(e, y, theta, os_, noise, mean)), theta_fn, os_fn, False
+        form = self._series_form()
+        if form is None:
+            return None
+        c, coeff_fn, os_fn = form
+        y = self.train_y.to(c.device).contiguous()
+        base = getattr(self.covar_module, "base_kernel", self.covar_module)
+        kappa_fn = lambda: base.lengthscale.double().reshape(())                               # noqa: E731
+        return (lambda kappa, os_, noise, mean: ops.gp_mll_series(c, y, *coeff_fn(kappa), os_, noise, mean)), kappa_fn, os_fn, True
+
     def _fast_mll_closure(self):
         """() -> (value, backward_fn) evaluating `marginal_log_likelihood` and the gradients of all parameters with one
         gabo_gp_mll launch: the device returns d ll / d (theta, outputscale, noise, mean); the chain rule through the parameter
         transforms and the priors is a handful of scalar torch operations on the parameters' own device."""
-        from . import ops
-        form = self._stationary_form()
+        form = self._fast_evaluator()
         if form is None:
             return None
-        e, theta_fn, os_fn = form
-        y = self.train_y.to(e.device).contiguous()
-        n = y.numel()
+        launch, theta_fn, os_fn, _ = form
+        n = self.train_y.numel()
 
         def evaluate():
             theta, os_, noise, mean = theta_fn(), os_fn(), self.noise, self.mean_constant
-            ll, g_theta, g_os, g_noise, g_mean, bad = ops.gp_mll(e, y, theta.item(), os_.item(), noise.item(), mean.item())
+            ll, g_theta, g_os, g_noise, g_mean, bad = launch(theta.item(), os_.item(), noise.item(), mean.item())
             if bad:
                 raise torch.linalg.LinAlgError("K + noise I is not positive definite")
             pri = self._priors()
@@ -562,14 +605,15 @@ class SingleTaskGP(torch.nn.Module):
         then lists the SCALAR hyper-parameters only."""
         import numpy as np
 
-        from . import _compat, ops
+        from . import _compat
         if _compat.HAVE_GPYTORCH:
             return None
+        series = False
         if evaluator is None:
-            form = self._stationary_form()
+            form = self._fast_evaluator()
             if form is None:
                 return None
-            e = form[0]
+            evaluator, series = form[0], form[3]
         cm = self.covar_module
         base = getattr(cm, "base_kernel", cm)
         index = {id(p): i for i, p in enumerate(params)}
@@ -606,9 +650,6 @@ class SingleTaskGP(torch.nn.Module):
                 return None
             priors.append(("noise", self.noise_prior.concentration, self.noise_prior.rate))
         n = self.train_y.numel()
-        if evaluator is None:
-            y = self.train_y.to(e.device).contiguous()
-            evaluator = lambda theta, os_, noise, mean: ops.gp_mll(e, y, theta, os_, noise, mean)      # noqa: E731
 
         def objective(v):
             val, dval = {}, {}
@@ -616,8 +657,8 @@ class SingleTaskGP(torch.nn.Module):
                 raw = float(np.float32(v[i])) if is32 else float(v[i])
                 val[name] = lb + max(raw, 0.0) + math.log1p(math.exp(-abs(raw)))           # softplus
                 dval[name] = 1.0 / (1.0 + math.exp(-raw)) if raw >= 0 else math.exp(raw) / (1.0 + math.exp(raw))
-            positive = val["theta"]                       # beta, or the lengthscale l with theta = l^-2
-            theta, dtheta = (positive, 1.0) if uses_beta else (positive ** -2, -2.0 * positive ** -3)
+            positive = val["theta"]                       # beta, the lengthscale kappa of a series, or the lengthscale l with theta = l^-2
+            theta, dtheta = (positive, 1.0) if uses_beta or series else (positive ** -2, -2.0 * positive ** -3)
             ll, g_theta, g_os, g_noise, g_mean, bad = evaluator(theta, val.get("os", 1.0), val["noise"], float(v[i_mean]))
             grad = np.zeros_like(v)
             if bad:

@@ -455,10 +455,29 @@ def sphere_matern_coefficients(dim, lengthscale, nu, num_levels, order=0, wrt_le
     order = 1, 2: the series of the first / second derivative in c = <x, y>; wrt_lengthscale: of the derivative in kappa (order 0: they sum to 0).
     -> (numpy float64 coefficients, series_dim) for sphere_zonal_from_inner / sphere_zonal_pairwise.  Host arithmetic only: the weights are
     formed in log space (m_n from exact integers) relative to the largest one, so nothing overflows at dim 64 or 128 levels."""
-    import math
-
     import numpy as np
-    dim, L, order = int(dim), int(num_levels), int(order)
+    order = int(order)
+    if order not in (0, 1, 2):
+        raise ValueError(f"sphere_matern_coefficients: order = {order} outside 0, 1, 2")
+    p, rate, series_dim = _sphere_matern_weights(*_sphere_matern_arguments(dim, lengthscale, nu, num_levels))
+    if wrt_lengthscale:
+        p = p * (rate - (p * rate).sum())
+    for _ in range(order):
+        p, series_dim = _zonal_derivative(p, series_dim)
+    return np.ascontiguousarray(p, dtype=np.float64), series_dim
+
+
+def sphere_matern_coefficients_and_derivative(dim, lengthscale, nu, num_levels):
+    """(p, dp / dkappa, series_dim): sphere_matern_coefficients(...) and its wrt_lengthscale=True form, bit for bit, from one pass over the
+    weights - what one evaluation of gp_mll_series takes."""
+    import numpy as np
+    p, rate, series_dim = _sphere_matern_weights(*_sphere_matern_arguments(dim, lengthscale, nu, num_levels))
+    return np.ascontiguousarray(p, dtype=np.float64), np.ascontiguousarray(p * (rate - (p * rate).sum()), dtype=np.float64), series_dim
+
+
+def _sphere_matern_arguments(dim, lengthscale, nu, num_levels):
+    import math
+    dim, L = int(dim), int(num_levels)
     kappa, nu = float(lengthscale), float(nu)
     if dim < 2:
         raise ValueError(f"sphere_matern_coefficients: dim = {dim}; the sphere S^(dim-1) needs dim >= 2")
@@ -468,12 +487,28 @@ def sphere_matern_coefficients(dim, lengthscale, nu, num_levels, order=0, wrt_le
         raise ValueError(f"sphere_matern_coefficients: nu = {nu} must be positive (math.inf: the heat kernel)")
     if not (kappa > 0.0 and math.isfinite(kappa)):
         raise ValueError(f"sphere_matern_coefficients: lengthscale = {kappa} must be positive and finite")
-    if order not in (0, 1, 2):
-        raise ValueError(f"sphere_matern_coefficients: order = {order} outside 0, 1, 2")
+    return dim, kappa, nu, L
+
+
+_sphere_level_logm = {}
+
+
+def _sphere_matern_weights(dim, kappa, nu, L):
+    """(p_n, Phi'(lambda_n) / Phi(lambda_n) in kappa, d) of sphere_matern_coefficients for validated arguments.  The log multiplicities
+    log m_n - exact integers, a Python loop - do not depend on kappa: kept per (dim, num_levels)."""
+    import math
+
+    import numpy as np
     d = dim - 1
     n = np.arange(L + 1, dtype=np.float64)
     lam = n * (n + (d - 1.0))
-    logm = np.array([0.0] + [math.log(math.comb(k + d, d) - math.comb(k + d - 2, d)) for k in range(1, L + 1)])
+    logm = _sphere_level_logm.get((dim, L))
+    if logm is None:
+        if len(_sphere_level_logm) > 64:
+            _sphere_level_logm.clear()
+        logm = np.array([0.0] + [math.log(math.comb(k + d, d) - math.comb(k + d - 2, d)) for k in range(1, L + 1)])
+        logm.setflags(write=False)
+        _sphere_level_logm[(dim, L)] = logm
     if math.isinf(nu):
         logphi = -(kappa * kappa) * lam / 2.0
         rate = -kappa * lam                                            # Phi' / Phi
@@ -483,13 +518,7 @@ def sphere_matern_coefficients(dim, lengthscale, nu, num_levels, order=0, wrt_le
         rate = (nu + d / 2.0) * (4.0 * nu / kappa ** 3) / base
     logw = logphi + logm
     w = np.exp(logw - logw.max())
-    p = w / w.sum()
-    if wrt_lengthscale:
-        p = p * (rate - (p * rate).sum())
-    series_dim = d
-    for _ in range(order):
-        p, series_dim = _zonal_derivative(p, series_dim)
-    return np.ascontiguousarray(p, dtype=np.float64), series_dim
+    return w / w.sum(), rate, d
 
 
 def sphere_zonal_table(coeff, series_dim):
@@ -1370,6 +1399,40 @@ def gp_mll_gram(k, y, outputscale, noise, mean, want_w=True):
         _lib.check(lib.gabo_gp_mll_gram(k.data_ptr(), y.data_ptr(), n, float(outputscale), float(noise), float(mean), out.data_ptr(),
                                         None if w is None else w.data_ptr(), _stream_ptr(dev)), "gabo_gp_mll_gram")
     return out, w
+
+
+def gp_mll_series(c, y, coeff, dcoeff, series_dim, outputscale, noise, mean):
+    """One evaluation of the exact-GP marginal log likelihood with K = outputscale * sum_k coeff[k] P_k^(series_dim)(c) + noise * I, the
+    zonal series evaluated inside the launch (gabo_gp_mll_series): -> [ll, dll/dkappa, dll/doutputscale, dll/dnoise, dll/dmean,
+    not_positive_definite] as Python floats, dll/dkappa from the series dcoeff of d coeff / d kappa (None: 0).  c: the n x n inner products,
+    fp64 on a HIP device, y: n; coeff, dcoeff: host float64 (sphere_matern_coefficients_and_derivative).  Beyond GABO_GP_MLL_MAX_N points (up
+    to GABO_GP_MLL_LARGE_MAX_N) the same numbers are composed from the element-wise series, gabo_gp_mll_large and one reduction."""
+    lib = _lib.load()
+    dev = c.device
+    n = c.shape[-1]
+    if c.dim() != 2 or c.shape[0] != n or y.numel() != n or not c.is_contiguous() or not y.is_contiguous():
+        raise RuntimeError("gp_mll_series: c must be a contiguous n x n matrix and y a contiguous vector of n targets")
+    a, ptr, na = _zonal_coeff(coeff)
+    da, dptr, nda = _zonal_coeff(dcoeff) if dcoeff is not None else (None, None, na)
+    if nda != na:
+        raise RuntimeError(f"gp_mll_series: {na} coefficients but {nda} derivative coefficients")
+    if n > _lib.GABO_GP_MLL_MAX_N:
+        out, w = _gp_mll_large(sphere_zonal_from_inner(c, a, series_dim), y, 0.0, outputscale, noise, mean, True, da is not None)
+        if da is not None:
+            d_kappa = (0.5 * float(outputscale)) * (w * sphere_zonal_from_inner(c, da, series_dim)).sum()
+            out[1] = torch.where(out[5] == 0, d_kappa, torch.zeros_like(d_kappa))
+        return out.tolist()
+    ent = _mll_host_out.get(dev.index)             # (the page-locked result buffer of gp_mll: one launch, one stream wait)
+    if ent is None:
+        host = torch.zeros(8, dtype=torch.float64).pin_memory()
+        ent = _mll_host_out[dev.index] = (host, host.numpy())
+    host, host_np = ent
+    with _on(dev):
+        stream = _stream_ptr(dev)
+        _lib.check(lib.gabo_gp_mll_series(c.data_ptr(), y.data_ptr(), n, ptr, dptr, na, int(series_dim), float(outputscale), float(noise),
+                                          float(mean), host.data_ptr(), stream), "gabo_gp_mll_series")
+        torch.cuda.current_stream(dev).synchronize()
+    return host_np[:6].tolist()
 
 
 def gram_extreme_eigenvalues(e, thetas):

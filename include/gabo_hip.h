@@ -296,7 +296,18 @@ int gabo_gp_mll(const double* e, const double* y, int64_t n, double theta, doubl
  * d out[0] / d k = outputscale * W / 2 chains into the kernel's own backward - no Cholesky / solve / log-det autograd. */
 int gabo_gp_mll_gram(const double* k, const double* y, int64_t n, double outputscale, double noise, double mean, double* out, double* w,
                      gabo_stream_t stream);
-/* Both of the above for larger training sets, n <= GABO_GP_MLL_LARGE_MAX_N: the same sweep operator on 32 x 32 tiles of the bordered
+/* The same for a base Gram matrix that is a zonal series of inner products fixed during the fit (the Riemannian Matern / heat kernels on
+ * the sphere, gabo_sphere_zonal_* above): c = X X^T (n x n, row-major; the lower triangle and the diagonal are read, the diagonal as given),
+ *   K_ij = sum_k coeff[k] P_k^(series_dim)(c_ij),  Ky = outputscale * K + noise * I,
+ * evaluated inside the launch with the recurrence of gabo_sphere_zonal_from_inner, operation for operation: K_ij has the bits that entry
+ * returns for c_ij, and out[0], out[2..5] those of gabo_gp_mll_gram on its result.  No Gram matrix, W or dK in memory.
+ *   out[1] = d out[0] / d kappa = outputscale * sum_ij W_ij dK_ij / 2,  dK_ij = sum_k dcoeff[k] P_k(c_ij)   (dcoeff_host NULL: out[1] = 0)
+ * coeff_host, dcoeff_host: n_coeff doubles each in HOST memory, copied into the kernel arguments.  One workgroup, csrc/gp_mll_series.hip.
+ * GABO_ERR_DIM for n < 1, n > GABO_GP_MLL_MAX_N or series_dim < 1; GABO_ERR_ARG for a null c, y, out or coeff_host and for n_coeff outside
+ * 1 ... 129 - all before any HIP call. */
+int gabo_gp_mll_series(const double* c, const double* y, int64_t n, const double* coeff_host, const double* dcoeff_host, int n_coeff,
+                       int series_dim, double outputscale, double noise, double mean, double* out, gabo_stream_t stream);
+/* Both of the first two above for larger training sets, n <= GABO_GP_MLL_LARGE_MAX_N: the same sweep operator on 32 x 32 tiles of the bordered
  * matrix in the caller's workspace, one launch per block of 32 pivots (csrc/gp_mll_large.hip).  gram = 0: e as in gabo_gp_mll;
  * gram != 0: e is the base Gram matrix as in gabo_gp_mll_gram (theta unused, out[1] = 0).  w: NULL or n x n as above.  Both triangles
  * of e are read. */
