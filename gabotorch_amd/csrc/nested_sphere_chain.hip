@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "gabo_device.hpp"
+#include "sphere_zonal_level.hpp"
 #include "../../include/gabo_hip.h"
 
 namespace gabo {
@@ -384,6 +385,61 @@ __global__ __launch_bounds__(64) void sphere_gram_adjoint_kernel(const double* _
     }
 }
 
+// The same adjoint for a zonal series f(c) = sum_k p_k P_k^(d)(c), d = lat - 1 (the Riemannian Matern / heat kernels, sphere_zonal.hip), straight
+// from the likelihood's W:  g_ij = half_os (W_ij + W_ji),  c_ij = <z_i, z_j>,
+//   gz_i = sum_j g_ij f'(c_ij) z_j,      d ll / d kappa = 1/2 sum_ij g_ij (d f / d kappa)(c_ij).
+// f' and d f / d kappa advance in one pass over the levels (sph_zonal_strip<2>): `table` holds 2 x L (coefficient, B_k) pairs, row 0 the levels of
+// f' with the B_k of dimension d + 2, row 1 those of d f / d kappa with the B_k of dimension d.  j = i is a term like any other and nothing is
+// clamped: f'(c_ii) != 0 and z_i is a unit vector only up to the projection's 1e-6 terms, so the radial part reaches the axes; g_ii carries
+// both arguments of K_ii.  One wave per row i; the lanes' partial sums are added in lane order, the rows' kappa sums in row order by the block
+// that finishes last (kappa_rows, counter zeroed by the caller): the same bits on every call.
+__global__ __launch_bounds__(64) void nested_sphere_zonal_adjoint_kernel(const double* __restrict__ z, const double* __restrict__ wm,
+                                                                        const double* __restrict__ table, double* __restrict__ gz,
+                                                                        double* kappa_rows, int* __restrict__ counter, double* __restrict__ out,
+                                                                        int n, int lat, int L, double half_os) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* zi = lds;                 // lat
+    double* acc = zi + lat;           // 64 x lat partial sums of gz_i
+    double* kap = acc + 64 * lat;     // 64 partial sums of the kappa term
+    int* last = reinterpret_cast<int*>(kap + 64);          // (in the dynamic region: a static would move its base off 16 bytes)
+    const int i = blockIdx.x, lane = threadIdx.x;
+    for (int l = lane; l < lat; l += 64) zi[l] = z[(size_t)i * lat + l];
+    for (int l = 0; l < lat; ++l) acc[lane * lat + l] = 0.0;
+    __syncthreads();
+    double kp = 0.0;
+    for (int j = lane; j < n; j += 64) {
+        const double* zj = z + (size_t)j * lat;
+        double c = 0.0;
+        for (int l = 0; l < lat; ++l) c = __builtin_fma(zi[l], zj[l], c);
+        double f[2];
+        sph_zonal_strip<2>(table, L, c, f);
+        const double g = half_os * (wm[(size_t)i * n + j] + wm[(size_t)j * n + i]);
+        const double w = g * f[0];
+        for (int l = 0; l < lat; ++l) acc[lane * lat + l] = __builtin_fma(w, zj[l], acc[lane * lat + l]);
+        kp = __builtin_fma(g, f[1], kp);
+    }
+    kap[lane] = kp;
+    __syncthreads();
+    for (int l = lane; l < lat; l += 64) {
+        double s = 0.0;
+        for (int q = 0; q < 64; ++q) s += acc[q * lat + l];
+        gz[(size_t)i * lat + l] = s;
+    }
+    if (lane == 0) {
+        double s = 0.0;
+        for (int q = 0; q < 64; ++q) s += kap[q];
+        __hip_atomic_store(kappa_rows + i, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        *last = atomicAdd(counter, 1) == n - 1;
+    }
+    __syncthreads();
+    if (!*last || lane != 0) return;
+    __threadfence();
+    double s = 0.0;
+    for (int r = 0; r < n; ++r) s += __hip_atomic_load(kappa_rows + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (past this CU's L1)
+    out[6] = 0.5 * s;
+}
+
 // dynamic LDS of a chain kernel beyond the 64 KB default needs the attribute (D >~ 90)
 template <typename K>
 static bool chain_lds_ok(K kernel, size_t bytes) {
@@ -419,6 +475,31 @@ struct SphereFitLayout {
         out = take(7 + tot);
         const size_t pg = blocks_gram, pp = (size_t)n * (tot + 2 * (size_t)L);
         partial = take(pg > pp ? pg : pp);
+        counters = take(2);
+        mll = o;
+        o += chain_align256(n > GABO_GP_MLL_MAX_N ? gabo_gp_mll_large_workspace_bytes(n) : 0);
+        total = o;
+    }
+};
+
+// device workspace of gabo_nested_sphere_fit_evaluate_series: no symmetrised copy of W, the series table behind the axes and distances
+struct SphereSeriesFitLayout {
+    size_t axes, table_at, frames, z, store, kb, wm, gz, out, partial, kappa, counters, mll, total;
+    SphereSeriesFitLayout(int64_t n, int D, int L, int n_coeff) {
+        const size_t tot = (size_t)chain_offset(D, L), nn = (size_t)n * n, lat = (size_t)(D - L);
+        table_at = (tot + (size_t)L + 1) & ~(size_t)1;                 // in doubles from `axes`: (coefficient, B_k) pairs on 16 bytes
+        size_t o = 0;
+        auto take = [&o](size_t doubles) { const size_t at = o; o += chain_align256(doubles * sizeof(double)); return at; };
+        axes = take(table_at + 4 * (size_t)n_coeff);
+        frames = take(tot + 2 * (size_t)L);
+        z = take((size_t)n * lat);
+        store = take((size_t)n * tot);
+        kb = take(nn);
+        wm = take(nn);
+        gz = take((size_t)n * lat);
+        out = take(7 + tot);
+        partial = take((size_t)n * (tot + 2 * (size_t)L));
+        kappa = take((size_t)n);
         counters = take(2);
         mll = o;
         o += chain_align256(n > GABO_GP_MLL_MAX_N ? gabo_gp_mll_large_workspace_bytes(n) : 0);
@@ -553,6 +634,88 @@ int gabo_nested_sphere_fit_evaluate(const double* x, const double* y, const doub
         out_doubles = 7 + total;
     }
     double* h_out = pinned + total + levels;
+    if (hipMemcpyAsync(h_out, d_out, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, s) != hipSuccess) return GABO_ERR_LAUNCH;
+    if (hipStreamSynchronize(s) != hipSuccess) return GABO_ERR_LAUNCH;
+    std::memcpy(out_host, h_out, sizeof(double) * out_doubles);
+    if (!want_grad) {
+        out_host[6] = 0.0;
+        std::memset(out_host + 7, 0, sizeof(double) * total);
+    }
+    return GABO_OK;
+}
+
+size_t gabo_nested_sphere_fit_series_workspace_bytes(int64_t n, int D, int levels, int n_coeff) {
+    if (n < 1 || D < 2 || levels < 1 || levels > D - 1 || n_coeff < 1 || n_coeff > gabo::kZonalMaxCoeff) return 0;
+    return gabo::SphereSeriesFitLayout(n, D, levels, n_coeff).total;
+}
+
+int gabo_nested_sphere_fit_evaluate_series(const double* x, const double* y, const double* axes_host, const double* distances_host, int64_t n,
+                                           int D, int levels, const double* coeff_host, const double* dcoeff_host, int n_coeff,
+                                           double outputscale, double noise, double mean, int want_grad, double* out_host, void* workspace,
+                                           size_t workspace_bytes, double* pinned, size_t pinned_doubles, gabo_stream_t stream) {
+    if (D < 2 || D > 4096 || levels < 1 || levels > D - 1) return GABO_ERR_DIM;
+    if (n < 1 || n > GABO_GP_MLL_LARGE_MAX_N) return GABO_ERR_DIM;
+    const int lat = D - levels, sd = lat - 1;             // the latent sphere S^(lat-1): series dimension lat - 1 >= 1
+    if (lat < 2 || lat > 64) return GABO_ERR_DIM;
+    const size_t total = (size_t)gabo::chain_offset(D, levels);
+    if (!x || !y || !axes_host || !distances_host || !coeff_host || !dcoeff_host || !out_host || !workspace || !pinned) return GABO_ERR_ARG;
+    if (n_coeff < 1 || n_coeff > gabo::kZonalMaxCoeff) return GABO_ERR_ARG;
+    const gabo::SphereSeriesFitLayout lay(n, D, levels, n_coeff);
+    const size_t upload = lay.table_at + 4 * (size_t)n_coeff;
+    if (workspace_bytes < lay.total || pinned_doubles < upload + 7 + total) return GABO_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    char* base = static_cast<char*>(workspace);
+    auto at = [base](size_t off) { return reinterpret_cast<double*>(base + off); };
+    double* d_axes = at(lay.axes);             // [axes (total) | distances (levels) | pad | table (2 x n_coeff pairs)]
+    double* d_dists = d_axes + total;
+    double* d_table = d_axes + lay.table_at;
+    double* d_out = at(lay.out);
+    int* counter = reinterpret_cast<int*>(base + lay.counters);
+    std::memcpy(pinned, axes_host, sizeof(double) * total);
+    std::memcpy(pinned + total, distances_host, sizeof(double) * levels);
+    {
+        // row 0: f' = sum_{k >= 1} p_k k (k + d - 1) / d P_{k-1}^(d+2)  (ops._zonal_derivative, operation for operation), zero-padded to n_coeff
+        // levels; row 1: d f / d kappa in dimension d.  B_k = (k - 1) / (k + dimension - 2), B_0 = B_1 = 0 (zonal_series of sphere_zonal.hip)
+        double* t0 = pinned + lay.table_at;
+        double* t1 = t0 + 2 * (size_t)n_coeff;
+        if (lay.table_at > total + levels) pinned[total + levels] = 0.0;
+        for (int k = 0; k < n_coeff; ++k) {
+            const double kk = (double)(k + 1);
+            t0[2 * k] = k + 1 < n_coeff ? coeff_host[k + 1] * (kk * (kk + ((double)sd - 1.0))) / (double)sd : 0.0;
+            t0[2 * k + 1] = k >= 2 ? ((double)k - 1.0) / ((double)k + (double)(sd + 2) - 2.0) : 0.0;
+            t1[2 * k] = dcoeff_host[k];
+            t1[2 * k + 1] = k >= 2 ? ((double)k - 1.0) / ((double)k + (double)sd - 2.0) : 0.0;
+        }
+    }
+    if (hipMemcpyAsync(d_axes, pinned, sizeof(double) * upload, hipMemcpyHostToDevice, s) != hipSuccess) return GABO_ERR_LAUNCH;
+    hipLaunchKernelGGL(gabo::nested_sphere_frames_kernel, dim3((unsigned)levels), dim3(64), 0, s, d_axes, at(lay.frames), D, levels);
+    const size_t nfr = total + 2 * (size_t)levels;
+    const size_t lds_fwd = (size_t)(D + levels) * sizeof(double), lds_bwd = ((size_t)(2 * D + levels) + nfr) * sizeof(double);
+    if (!gabo::chain_lds_ok(gabo::nested_sphere_project_backward_kernel, lds_bwd)) return GABO_ERR_DIM;
+    hipLaunchKernelGGL(gabo::nested_sphere_project_kernel, dim3((unsigned)n), dim3(64), lds_fwd, s, x, at(lay.frames), d_dists,
+                       at(lay.z), want_grad ? at(lay.store) : nullptr, D, levels);
+    if (hipGetLastError() != hipSuccess) return GABO_ERR_LAUNCH;
+    int rc = gabo_sphere_zonal_pairwise(at(lay.z), at(lay.z), at(lay.kb), 1, n, n, lat, 0, 0, coeff_host, n_coeff, sd, GABO_SYMMETRIC, 0, stream);
+    if (rc != GABO_OK) return rc;
+    double* wm = want_grad ? at(lay.wm) : nullptr;
+    if (n <= GABO_GP_MLL_MAX_N)
+        rc = gabo_gp_mll_gram(at(lay.kb), y, n, outputscale, noise, mean, d_out, wm, stream);
+    else
+        rc = gabo_gp_mll_large(at(lay.kb), y, n, 0.0, outputscale, noise, mean, 1, d_out, wm, base + lay.mll, gabo_gp_mll_large_workspace_bytes(n), stream);
+    if (rc != GABO_OK) return rc;
+    size_t out_doubles = 6;
+    if (want_grad) {
+        if (hipMemsetAsync(counter, 0, 2 * sizeof(double), s) != hipSuccess) return GABO_ERR_LAUNCH;
+        hipLaunchKernelGGL(gabo::nested_sphere_zonal_adjoint_kernel, dim3((unsigned)n), dim3(64), (size_t)(65 * lat + 66) * sizeof(double), s, at(lay.z),
+                           wm, d_table, at(lay.gz), at(lay.kappa), counter, d_out, (int)n, lat, n_coeff, 0.5 * outputscale);
+        hipLaunchKernelGGL(gabo::nested_sphere_project_backward_kernel, dim3((unsigned)n), dim3(64), lds_bwd, s, at(lay.store),
+                           at(lay.frames), d_dists, at(lay.gz), at(lay.partial), D, levels);
+        hipLaunchKernelGGL(gabo::nested_sphere_axes_adjoint_kernel, dim3((unsigned)levels), dim3(64), (size_t)D * sizeof(double), s, d_axes, at(lay.frames),
+                           at(lay.partial), d_out + 7, (int)n, D, levels);
+        if (hipGetLastError() != hipSuccess) return GABO_ERR_LAUNCH;
+        out_doubles = 7 + total;
+    }
+    double* h_out = pinned + upload;
     if (hipMemcpyAsync(h_out, d_out, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, s) != hipSuccess) return GABO_ERR_LAUNCH;
     if (hipStreamSynchronize(s) != hipSuccess) return GABO_ERR_LAUNCH;
     std::memcpy(out_host, h_out, sizeof(double) * out_doubles);

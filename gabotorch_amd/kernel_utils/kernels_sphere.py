@@ -24,6 +24,16 @@ class SphereLaplaceKernel(Kernel):
         return ops.sphere_kernel(x1, x2, 1.0 / (ls * ls), _lib.GABO_OUT_LAPLACE, diag=diag)
 
 
+def _matern_arguments(who, nu, num_levels):
+    """(nu, num_levels) of a Riemannian Matern kernel class, validated"""
+    nu = float(nu)
+    if not nu > 0.0:
+        raise ValueError(f"{who}: nu = {nu} must be positive (math.inf: the heat kernel)")
+    if int(num_levels) != num_levels or not 1 <= int(num_levels) <= ops.SPHERE_ZONAL_MAX_LEVELS:
+        raise ValueError(f"{who}: num_levels = {num_levels} outside 1 ... {ops.SPHERE_ZONAL_MAX_LEVELS}")
+    return nu, int(num_levels)
+
+
 class SphereRiemannianMaternKernel(Kernel):
     """Riemannian Matern kernel on the sphere (Borovitskiy et al., NeurIPS 2020; Jaquier et al., CoRL 2021), gpytorch `lengthscale`
     parameter; nu = math.inf is the heat (squared-exponential) kernel.  k(x, y) = sum_{n <= num_levels} p_n P_n(<x, y>) with P_n the
@@ -32,14 +42,10 @@ class SphereRiemannianMaternKernel(Kernel):
     nu and num_levels are fixed, not parameters."""
 
     def __init__(self, nu=2.5, num_levels=32, **kwargs):
-        nu = float(nu)
-        if not nu > 0.0:
-            raise ValueError(f"SphereRiemannianMaternKernel: nu = {nu} must be positive (math.inf: the heat kernel)")
-        if int(num_levels) != num_levels or not 1 <= int(num_levels) <= ops.SPHERE_ZONAL_MAX_LEVELS:
-            raise ValueError(f"SphereRiemannianMaternKernel: num_levels = {num_levels} outside 1 ... {ops.SPHERE_ZONAL_MAX_LEVELS}")
+        nu, num_levels = _matern_arguments("SphereRiemannianMaternKernel", nu, num_levels)
         self.has_lengthscale = True
         super().__init__(has_lengthscale=True, ard_num_dims=None, **kwargs)
-        self.nu, self.num_levels = nu, int(num_levels)
+        self.nu, self.num_levels = nu, num_levels
 
     def forward(self, x1, x2, diag=False, **params):
         # (x1 is x2 - the Gram matrix of one set - takes the symmetric launch inside)

@@ -180,15 +180,17 @@ class _NestedSphereMllProblem(_MllProblem):
     (examples/hd_bo_sphere/benchmark_examples/hd_gabo_sphere.py:150-180): the axes of the nested spheres are learnt on their spheres together
     with the scalar hyper-parameters.  One evaluation is ONE host call (gabo_nested_sphere_fit_evaluate: every level of the projection for
     every training point in one launch, the Gram matrix, the likelihood, and their adjoints back to the axes); torch autograd through the
-    level-by-level Python statement of the projection needed ~50 launches per level."""
+    level-by-level Python statement of the projection needed ~50 launches per level.
+    ScaleKernel(NestedSphereRiemannianMaternKernel) takes gabo_nested_sphere_fit_evaluate_series: the scalar parameter handed to the call is the
+    lengthscale kappa itself, as the coefficients (p, dp / dkappa) of the series on the latent sphere, formed on the host per evaluation."""
 
     @staticmethod
     def build(model, names, params, manifold):
         from .. import _compat, ops
-        from ..kernel_utils.kernels_nested_sphere import NestedSphereGaussianKernel
+        from ..kernel_utils.kernels_nested_sphere import NestedSphereGaussianKernel, NestedSphereRiemannianMaternKernel
         cm = model.covar_module
         base = getattr(cm, "base_kernel", None)
-        if _compat.HAVE_GPYTORCH or base is None or type(base) is not NestedSphereGaussianKernel:
+        if _compat.HAVE_GPYTORCH or base is None or type(base) not in (NestedSphereGaussianKernel, NestedSphereRiemannianMaternKernel):
             return None
         if not model.train_x.is_cuda and not torch.cuda.is_available():
             return None
@@ -216,7 +218,14 @@ class _NestedSphereMllProblem(_MllProblem):
         self.dists = np.array([float(d.reshape(-1)[0]) for d in base.distances_to_axis], dtype=np.float64)
         self.total = sum(self.D - k for k in range(self.L))
         self.want_grad, self.values_only, self.axes_host, self.grad_axes, self._buffers, self._recent = False, False, None, None, None, []
-        self.scalar = model._fast_scalar_objective([params[k] for k in self.scalar_idx], evaluator=self._evaluate)
+        self.series = None
+        if type(base) is NestedSphereRiemannianMaternKernel:
+            if base.raw_lengthscale.numel() != 1:
+                return None
+            self.series = (int(base.latent_dim), float(base.nu), int(base.num_levels))
+            self.scalar = model._fast_scalar_objective([params[k] for k in self.scalar_idx], evaluator=self._evaluate, evaluator_takes_value=True)
+        else:
+            self.scalar = model._fast_scalar_objective([params[k] for k in self.scalar_idx], evaluator=self._evaluate)
         return self if self.scalar is not None else None
 
     def _evaluate(self, theta, outputscale, noise, mean):
@@ -225,8 +234,14 @@ class _NestedSphereMllProblem(_MllProblem):
         lib = _lib.load()
         n = self.x.shape[0]
         if self._buffers is None:
-            ws = torch.empty(max(int(lib.gabo_nested_sphere_fit_workspace_bytes(n, self.D, self.L)), 16), dtype=torch.uint8, device=self.x.device)
-            self._buffers = (ws, torch.empty(2 * self.total + self.L + 7, dtype=torch.float64).pin_memory(), np.empty(7 + self.total))
+            if self.series is None:
+                ws_bytes, pinned_doubles = lib.gabo_nested_sphere_fit_workspace_bytes(n, self.D, self.L), 2 * self.total + self.L + 7
+            else:                           # (num_levels + 1 coefficients; the pinned buffer also carries the two series of the adjoint)
+                n_coeff = self.series[2] + 1
+                ws_bytes = lib.gabo_nested_sphere_fit_series_workspace_bytes(n, self.D, self.L, n_coeff)
+                pinned_doubles = 2 * self.total + self.L + 1 + 4 * n_coeff + 7
+            ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=self.x.device)
+            self._buffers = (ws, torch.empty(pinned_doubles, dtype=torch.float64).pin_memory(), np.empty(7 + self.total))
         ws, pinned, out = self._buffers
         key = (self.axes_host.tobytes(), theta, outputscale, noise, mean)
         for k, res in self._recent:
@@ -236,10 +251,17 @@ class _NestedSphereMllProblem(_MllProblem):
         want = self.want_grad or not self.values_only
         ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
         with torch.cuda.device(self.x.device):
-            _lib.check(lib.gabo_nested_sphere_fit_evaluate(
-                self.x.data_ptr(), self.y.data_ptr(), ptr(self.axes_host), ptr(self.dists), n, self.D, self.L, float(theta), float(outputscale),
-                float(noise), float(mean), 1 if want else 0, ptr(out), ws.data_ptr(), ws.numel(), pinned.data_ptr(), pinned.numel(),
-                self.ops._stream_ptr(self.x.device)), "gabo_nested_sphere_fit_evaluate")
+            if self.series is None:
+                _lib.check(lib.gabo_nested_sphere_fit_evaluate(
+                    self.x.data_ptr(), self.y.data_ptr(), ptr(self.axes_host), ptr(self.dists), n, self.D, self.L, float(theta), float(outputscale),
+                    float(noise), float(mean), 1 if want else 0, ptr(out), ws.data_ptr(), ws.numel(), pinned.data_ptr(), pinned.numel(),
+                    self.ops._stream_ptr(self.x.device)), "gabo_nested_sphere_fit_evaluate")
+            else:                           # theta is the lengthscale kappa (evaluator_takes_value)
+                p, dp, _ = self.ops.sphere_matern_coefficients_and_derivative(self.series[0], float(theta), self.series[1], self.series[2])
+                _lib.check(lib.gabo_nested_sphere_fit_evaluate_series(
+                    self.x.data_ptr(), self.y.data_ptr(), ptr(self.axes_host), ptr(self.dists), n, self.D, self.L, ptr(p), ptr(dp), int(p.size),
+                    float(outputscale), float(noise), float(mean), 1 if want else 0, ptr(out), ws.data_ptr(), ws.numel(), pinned.data_ptr(),
+                    pinned.numel(), self.ops._stream_ptr(self.x.device)), "gabo_nested_sphere_fit_evaluate_series")
         res = ((float(out[0]), float(out[6]), float(out[2]), float(out[3]), float(out[4]), float(out[5])), out[7:].copy(), want)
         self._recent = [(key, res)] + self._recent[:3]
         self.grad_axes = res[1]

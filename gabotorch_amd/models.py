@@ -595,20 +595,21 @@ class SingleTaskGP(torch.nn.Module):
 
         return evaluate
 
-    def _fast_scalar_objective(self, params, evaluator=None):
+    def _fast_scalar_objective(self, params, evaluator=None, evaluator_takes_value=False):
         """v -> (loss, gradient) in plain Python floats for the layout every reference example uses (stand-in ScaleKernel / kernel
         classes with softplus constraints, Gamma priors): the chain rule through softplus and the priors costs microseconds, so an
         L-BFGS evaluation is the gabo_gp_mll launch and its 48-byte read-back.  None when the model is laid out differently (the
         caller then lets autograd do the chain rule).
         evaluator(theta, outputscale, noise, mean) -> (ll, d theta, d outputscale, d noise, d mean, not_pd): replaces the launch on the
         fixed distance matrix for kernels with further parameters inside the distance (the nested kernels: manifold_gp_fit.py); `params`
-        then lists the SCALAR hyper-parameters only."""
+        then lists the SCALAR hyper-parameters only.  evaluator_takes_value: that evaluator takes the constrained lengthscale kappa itself in
+        the place of theta = l^-2 and returns d / d kappa (a series kernel, as the built-in series evaluator)."""
         import numpy as np
 
         from . import _compat
         if _compat.HAVE_GPYTORCH:
             return None
-        series = False
+        series = bool(evaluator_takes_value) and evaluator is not None
         if evaluator is None:
             form = self._fast_evaluator()
             if form is None:

@@ -439,6 +439,15 @@ int gabo_nested_spd_fit_evaluate(const double* x_mandel, const double* x_matrice
  *   out_host (7 + sum_k (D - k) doubles): [ll, 0, d/d outputscale, d/d noise, d/d mean, not-positive-definite flag, d/d beta, d ll / d axes
  *   (packed, Euclidean)]; want_grad = 0: the first six only.  workspace: device, ..._fit_workspace_bytes; pinned: >= 2 sum_k (D - k) + levels + 7
  *   doubles of page-locked host memory.  D - levels <= 64, n <= GABO_GP_MLL_LARGE_MAX_N.
+ * gabo_nested_sphere_fit_evaluate_series: the same call for ScaleKernel(NestedSphereRiemannianMaternKernel): the kernel of the latent points
+ *   is the zonal series sum_k coeff[k] P_k^(d)(<z_i, z_j>) of gabo_sphere_zonal_pairwise, d = D - levels - 1 (the Riemannian Matern / heat
+ *   kernels; positive definite for every lengthscale kappa).  coeff_host, dcoeff_host: n_coeff doubles each in HOST memory, the coefficients
+ *   and their derivatives in kappa.  out_host as above with out[6] = d ll / d kappa.  The adjoint of the Gram matrix with respect to the latent
+ *   points, sum_j g_ij f'(<z_i, z_j>) z_j with the term j = i and no clamp, and the kappa sum are one launch (nested_sphere_zonal_adjoint_kernel,
+ *   csrc/nested_sphere_chain.hip), summed in a fixed order: two calls return the same bits.
+ *   workspace: ..._fit_series_workspace_bytes (0 for arguments the call rejects); pinned: >= 2 sum_k (D - k) + levels + 1 + 4 n_coeff + 7 doubles.
+ *   GABO_ERR_DIM for D - levels < 2 or > 64 and for n outside 1 ... GABO_GP_MLL_LARGE_MAX_N; GABO_ERR_ARG for a null pointer, n_coeff outside
+ *   1 ... 129 and a short workspace or pinned buffer - all before any HIP call.
  */
 int gabo_nested_sphere_frames(const double* axes, double* frames, int D, int levels, gabo_stream_t stream);
 /* gabo_nested_sphere_project: x (n x D) through every level -> z (n x (D - levels));  levels_in (or NULL): n x sum_k (D - k), the input of
@@ -457,6 +466,11 @@ size_t gabo_nested_sphere_fit_workspace_bytes(int64_t n, int D, int levels);
 int gabo_nested_sphere_fit_evaluate(const double* x, const double* y, const double* axes_host, const double* distances_host, int64_t n, int D,
                                     int levels, double beta, double outputscale, double noise, double mean, int want_grad, double* out_host,
                                     void* workspace, size_t workspace_bytes, double* pinned, size_t pinned_doubles, gabo_stream_t stream);
+size_t gabo_nested_sphere_fit_series_workspace_bytes(int64_t n, int D, int levels, int n_coeff);
+int gabo_nested_sphere_fit_evaluate_series(const double* x, const double* y, const double* axes_host, const double* distances_host, int64_t n,
+                                           int D, int levels, const double* coeff_host, const double* dcoeff_host, int n_coeff,
+                                           double outputscale, double noise, double mean, int want_grad, double* out_host, void* workspace,
+                                           size_t workspace_bytes, double* pinned, size_t pinned_doubles, gabo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * n random SPD matrices with the distribution of spd_sample (Riemannian_utils/spd_utils.py:290-306; the raw samples of
