@@ -13,6 +13,7 @@
 
 #include <cstring>
 
+#include "fit_chain.hpp"
 #include "gabo_device.hpp"
 #include "../../include/gabo_hip.h"
 
@@ -114,17 +115,13 @@ int fit_gram_adjoint_launch(const double* kb, const double* wm, double* gs, doub
 
 namespace {
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct FitLayout {
-    size_t w, z, feat, kb, wm, gs, gfeat, gz, out, partial, counters, mll, total;
+struct FitLayout : FitArena {
+    size_t w, z, feat, kb, wm, gs, gfeat, gz, out, partial, counters, mll;
     unsigned blocks_gram, blocks_proj;
     FitLayout(int64_t n, int D, int d) {
         const size_t dv = (size_t)d * (d + 1) / 2, nn = (size_t)n * n;
         blocks_gram = (unsigned)((nn + 255) / 256 > 256 ? 256 : (nn + 255) / 256);
         blocks_proj = (unsigned)(n > 64 ? 64 : (n < 1 ? 1 : n));
-        size_t o = 0;
-        auto take = [&o](size_t doubles) { const size_t at = o; o += align256(doubles * sizeof(double)); return at; };
         w = take((size_t)D * d);
         z = take((size_t)n * dv);
         feat = take((size_t)n * dv);
@@ -137,9 +134,7 @@ struct FitLayout {
         const size_t pg = blocks_gram, pp = (size_t)blocks_proj * D * d;
         partial = take(pg > pp ? pg : pp);
         counters = take(2);
-        mll = o;
-        o += align256(n > GABO_GP_MLL_MAX_N ? gabo_gp_mll_large_workspace_bytes(n) : 0);
-        total = o;
+        mll = take_mll(n);
     }
 };
 
@@ -160,14 +155,14 @@ int gabo_nested_spd_fit_evaluate(const double* x_mandel, const double* x_matrice
     if (n < 1 || n > GABO_GP_MLL_LARGE_MAX_N) return GABO_ERR_DIM;
     const size_t Dd = (size_t)D * d;
     if (!x_mandel || !x_matrices || !y || !w_host || !out_host || !workspace || !pinned || !(theta > 0.0)) return GABO_ERR_ARG;
-    const gabo::FitLayout lay(n, D, d);
+    gabo::FitLayout lay(n, D, d);
     if (workspace_bytes < lay.total || pinned_doubles < Dd + 7 + Dd) return GABO_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    char* base = static_cast<char*>(workspace);
-    auto at = [base](size_t off) { return reinterpret_cast<double*>(base + off); };
+    lay.base = static_cast<char*>(workspace);
+    auto at = [&lay](size_t off) { return lay.at(off); };
     double* d_w = at(lay.w);
     double* d_out = at(lay.out);
-    int* counters = reinterpret_cast<int*>(base + lay.counters);
+    int* counters = reinterpret_cast<int*>(lay.base + lay.counters);
     if (want_grad && hipMemsetAsync(counters, 0, 2 * sizeof(int), s) != hipSuccess) return GABO_ERR_LAUNCH;     // the two tickets
     std::memcpy(pinned, w_host, sizeof(double) * Dd);
     if (hipMemcpyAsync(d_w, pinned, sizeof(double) * Dd, hipMemcpyHostToDevice, s) != hipSuccess) return GABO_ERR_LAUNCH;
@@ -176,16 +171,11 @@ int gabo_nested_spd_fit_evaluate(const double* x_mandel, const double* x_matrice
     if (rc == GABO_OK) rc = gabo_frobenius_pairwise(at(lay.feat), at(lay.feat), at(lay.kb), 1, n, n, d, 0, 0, theta, GABO_OUT_GAUSSIAN, stream);
     if (rc != GABO_OK) return rc;
     double* wm = want_grad ? at(lay.wm) : nullptr;
-    if (n <= GABO_GP_MLL_MAX_N)
-        rc = gabo_gp_mll_gram(at(lay.kb), y, n, outputscale, noise, mean, d_out, wm, stream);
-    else
-        rc = gabo_gp_mll_large(at(lay.kb), y, n, 0.0, outputscale, noise, mean, 1, d_out, wm, base + lay.mll, gabo_gp_mll_large_workspace_bytes(n), stream);
+    rc = gabo::fit_likelihood(at(lay.kb), y, n, outputscale, noise, mean, d_out, wm, lay.base + lay.mll, stream);
     if (rc != GABO_OK) return rc;
-    size_t out_doubles = 6;
     if (want_grad) {
-        hipLaunchKernelGGL(gabo::fit_gram_adjoint_kernel, dim3(lay.blocks_gram), dim3(256), 0, s, at(lay.kb), wm, at(lay.gs), d_out, at(lay.partial),
-                           counters, n, 0.5 * outputscale, theta);
-        if (hipGetLastError() != hipSuccess) return GABO_ERR_LAUNCH;
+        rc = gabo::fit_gram_adjoint_launch(at(lay.kb), wm, at(lay.gs), d_out, at(lay.partial), counters, n, 0.5 * outputscale, theta, lay.blocks_gram, s);
+        if (rc != GABO_OK) return rc;
         // both arguments of the symmetric Gram matrix at once: gs is symmetrised, so the x1-gradient with it is the whole gradient
         // (up to the 1e-15 the reference adds to the difference, which enters the two arguments with opposite signs)
         rc = gabo_frobenius_backward(at(lay.feat), at(lay.feat), at(lay.gs), at(lay.gfeat), 1, n, n, d, 0, 0, n * n, n, 1, theta, GABO_OUT_GAUSSIAN,
@@ -196,17 +186,8 @@ int gabo_nested_spd_fit_evaluate(const double* x_mandel, const double* x_matrice
         hipLaunchKernelGGL(gabo::fit_projection_adjoint_kernel, dim3(lay.blocks_proj), dim3(256), lds, s, x_matrices, d_w, at(lay.gz), at(lay.partial),
                            d_out + 7, counters + 1, n, D, d);
         if (hipGetLastError() != hipSuccess) return GABO_ERR_LAUNCH;
-        out_doubles = 7 + Dd;
     }
-    double* h_out = pinned + Dd;
-    if (hipMemcpyAsync(h_out, d_out, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, s) != hipSuccess) return GABO_ERR_LAUNCH;
-    if (hipStreamSynchronize(s) != hipSuccess) return GABO_ERR_LAUNCH;
-    std::memcpy(out_host, h_out, sizeof(double) * out_doubles);
-    if (!want_grad) {
-        out_host[6] = 0.0;
-        std::memset(out_host + 7, 0, sizeof(double) * Dd);
-    }
-    return GABO_OK;
+    return gabo::fit_finish(d_out, pinned + Dd, out_host, Dd, want_grad, s);
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 // dimension D - k, offset sum_{j<k} (D - j)), followed by the (s, t) pairs.
 #include <cstring>
 
+#include "fit_chain.hpp"
 #include "gabo_device.hpp"
 #include "sphere_zonal_level.hpp"
 #include "../../include/gabo_hip.h"
@@ -453,59 +454,88 @@ int fit_gram_adjoint_launch(const double* kb, const double* wm, double* gs, doub
 
 namespace {
 
-size_t chain_align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// device workspace of gabo_nested_sphere_fit_evaluate
-struct SphereFitLayout {
-    size_t axes, frames, z, store, kb, wm, gs, gz, out, partial, counters, mll, total;
+// Device workspace of the two fit entries.  n_coeff = 0 is the Gaussian kernel (gabo_nested_sphere_fit_evaluate): gs, the symmetrised copy of W,
+// and `partial` large enough for the block partials of fit_gram_adjoint_kernel too.  n_coeff > 0 is a zonal series of that many levels
+// (gabo_nested_sphere_fit_evaluate_series): the series table behind the axes and distances, and the kappa sums of the rows.
+struct SphereFitLayout : FitArena {
+    size_t upload, table_at, axes, frames, z, store, kb, wm, gs = 0, gz, out, partial, kappa = 0, counters, mll;
     unsigned blocks_gram;
-    SphereFitLayout(int64_t n, int D, int L) {
+    SphereFitLayout(int64_t n, int D, int L, int n_coeff) {
         const size_t tot = (size_t)chain_offset(D, L), nn = (size_t)n * n, lat = (size_t)(D - L);
         blocks_gram = (unsigned)((nn + 255) / 256 > 256 ? 256 : (nn + 255) / 256);
-        size_t o = 0;
-        auto take = [&o](size_t doubles) { const size_t at = o; o += chain_align256(doubles * sizeof(double)); return at; };
-        axes = take(tot + L);
+        table_at = (tot + (size_t)L + 1) & ~(size_t)1;                 // in doubles from `axes`: (coefficient, B_k) pairs on 16 bytes
+        upload = n_coeff ? table_at + 4 * (size_t)n_coeff : tot + L;   // [axes (tot) | distances (L)] and, for a series, [pad | table]
+        axes = take(upload);
         frames = take(tot + 2 * (size_t)L);
         z = take((size_t)n * lat);
         store = take((size_t)n * tot);
         kb = take(nn);
         wm = take(nn);
-        gs = take(nn);
+        if (!n_coeff) gs = take(nn);
         gz = take((size_t)n * lat);
         out = take(7 + tot);
-        const size_t pg = blocks_gram, pp = (size_t)n * (tot + 2 * (size_t)L);
+        const size_t pg = n_coeff ? 0 : blocks_gram, pp = (size_t)n * (tot + 2 * (size_t)L);
         partial = take(pg > pp ? pg : pp);
+        if (n_coeff) kappa = take((size_t)n);
         counters = take(2);
-        mll = o;
-        o += chain_align256(n > GABO_GP_MLL_MAX_N ? gabo_gp_mll_large_workspace_bytes(n) : 0);
-        total = o;
+        mll = take_mll(n);
     }
 };
 
-// device workspace of gabo_nested_sphere_fit_evaluate_series: no symmetrised copy of W, the series table behind the axes and distances
-struct SphereSeriesFitLayout {
-    size_t axes, table_at, frames, z, store, kb, wm, gz, out, partial, kappa, counters, mll, total;
-    SphereSeriesFitLayout(int64_t n, int D, int L, int n_coeff) {
-        const size_t tot = (size_t)chain_offset(D, L), nn = (size_t)n * n, lat = (size_t)(D - L);
-        table_at = (tot + (size_t)L + 1) & ~(size_t)1;                 // in doubles from `axes`: (coefficient, B_k) pairs on 16 bytes
-        size_t o = 0;
-        auto take = [&o](size_t doubles) { const size_t at = o; o += chain_align256(doubles * sizeof(double)); return at; };
-        axes = take(table_at + 4 * (size_t)n_coeff);
-        frames = take(tot + 2 * (size_t)L);
-        z = take((size_t)n * lat);
-        store = take((size_t)n * tot);
-        kb = take(nn);
-        wm = take(nn);
-        gz = take((size_t)n * lat);
-        out = take(7 + tot);
-        partial = take((size_t)n * (tot + 2 * (size_t)L));
-        kappa = take((size_t)n);
-        counters = take(2);
-        mll = o;
-        o += chain_align256(n > GABO_GP_MLL_MAX_N ? gabo_gp_mll_large_workspace_bytes(n) : 0);
-        total = o;
+// row 0: f' = sum_{k >= 1} p_k k (k + d - 1) / d P_{k-1}^(d+2)  (ops._zonal_derivative, operation for operation), zero-padded to n_coeff
+// levels; row 1: d f / d kappa in dimension d = sd.  B_k = (k - 1) / (k + dimension - 2), B_0 = B_1 = 0 (zonal_series of sphere_zonal.hip)
+void sphere_series_adjoint_table(double* t0, const double* coeff, const double* dcoeff, int n_coeff, int sd) {
+    double* t1 = t0 + 2 * (size_t)n_coeff;
+    for (int k = 0; k < n_coeff; ++k) {
+        const double kk = (double)(k + 1);
+        t0[2 * k] = k + 1 < n_coeff ? coeff[k + 1] * (kk * (kk + ((double)sd - 1.0))) / (double)sd : 0.0;
+        t0[2 * k + 1] = k >= 2 ? ((double)k - 1.0) / ((double)k + (double)(sd + 2) - 2.0) : 0.0;
+        t1[2 * k] = dcoeff[k];
+        t1[2 * k + 1] = k >= 2 ? ((double)k - 1.0) / ((double)k + (double)sd - 2.0) : 0.0;
     }
-};
+}
+
+// The chain both entries issue on `stream` once their arguments are checked and pinned[0 .. lay.upload) holds what follows the axes and
+// distances: upload, frames, projection, gram(), likelihood, and for the gradient a memset of counter_bytes at the counters,
+// gram_adjoint(wm, d_out, counter) -> gz, the projection's and the axes' adjoints; then the read-back.  gram and gram_adjoint return a status.
+template <typename Gram, typename GramAdjoint>
+int sphere_fit_chain(SphereFitLayout& lay, const double* x, const double* y, const double* axes_host, const double* distances_host, int64_t n, int D,
+                     int levels, double outputscale, double noise, double mean, int want_grad, double* out_host, void* workspace, double* pinned,
+                     size_t counter_bytes, gabo_stream_t stream, Gram gram, GramAdjoint gram_adjoint) {
+    const size_t total = (size_t)chain_offset(D, levels);
+    hipStream_t s = (hipStream_t)stream;
+    lay.base = static_cast<char*>(workspace);
+    double* d_axes = lay.at(lay.axes);
+    double* d_dists = d_axes + total;
+    double* d_out = lay.at(lay.out);
+    int* counter = reinterpret_cast<int*>(lay.base + lay.counters);
+    std::memcpy(pinned, axes_host, sizeof(double) * total);
+    std::memcpy(pinned + total, distances_host, sizeof(double) * levels);
+    if (hipMemcpyAsync(d_axes, pinned, sizeof(double) * lay.upload, hipMemcpyHostToDevice, s) != hipSuccess) return GABO_ERR_LAUNCH;
+    hipLaunchKernelGGL(nested_sphere_frames_kernel, dim3((unsigned)levels), dim3(64), 0, s, d_axes, lay.at(lay.frames), D, levels);
+    const size_t nfr = total + 2 * (size_t)levels;
+    const size_t lds_fwd = (size_t)(D + levels) * sizeof(double), lds_bwd = ((size_t)(2 * D + levels) + nfr) * sizeof(double);
+    if (!chain_lds_ok(nested_sphere_project_backward_kernel, lds_bwd)) return GABO_ERR_DIM;
+    hipLaunchKernelGGL(nested_sphere_project_kernel, dim3((unsigned)n), dim3(64), lds_fwd, s, x, lay.at(lay.frames), d_dists, lay.at(lay.z),
+                       want_grad ? lay.at(lay.store) : nullptr, D, levels);
+    if (hipGetLastError() != hipSuccess) return GABO_ERR_LAUNCH;
+    int rc = gram();
+    if (rc != GABO_OK) return rc;
+    double* wm = want_grad ? lay.at(lay.wm) : nullptr;
+    rc = fit_likelihood(lay.at(lay.kb), y, n, outputscale, noise, mean, d_out, wm, lay.base + lay.mll, stream);
+    if (rc != GABO_OK) return rc;
+    if (want_grad) {
+        if (hipMemsetAsync(counter, 0, counter_bytes, s) != hipSuccess) return GABO_ERR_LAUNCH;
+        rc = gram_adjoint(wm, d_out, counter);
+        if (rc != GABO_OK) return rc;
+        hipLaunchKernelGGL(nested_sphere_project_backward_kernel, dim3((unsigned)n), dim3(64), lds_bwd, s, lay.at(lay.store), lay.at(lay.frames),
+                           d_dists, lay.at(lay.gz), lay.at(lay.partial), D, levels);
+        hipLaunchKernelGGL(nested_sphere_axes_adjoint_kernel, dim3((unsigned)levels), dim3(64), (size_t)D * sizeof(double), s, d_axes,
+                           lay.at(lay.frames), lay.at(lay.partial), d_out + 7, (int)n, D, levels);
+        if (hipGetLastError() != hipSuccess) return GABO_ERR_LAUNCH;
+    }
+    return fit_finish(d_out, pinned + lay.upload, out_host, total, want_grad, s);
+}
 
 }  // namespace
 }  // namespace gabo
@@ -580,7 +610,7 @@ int gabo_nested_sphere_reconstruction(const double* x_data, const double* x_subs
 
 size_t gabo_nested_sphere_fit_workspace_bytes(int64_t n, int D, int levels) {
     if (n < 1 || D < 2 || levels < 1 || levels > D - 1) return 0;
-    return gabo::SphereFitLayout(n, D, levels).total;
+    return gabo::SphereFitLayout(n, D, levels, 0).total;
 }
 
 int gabo_nested_sphere_fit_evaluate(const double* x, const double* y, const double* axes_host, const double* distances_host, int64_t n, int D,
@@ -592,61 +622,25 @@ int gabo_nested_sphere_fit_evaluate(const double* x, const double* y, const doub
     if (lat > 64) return GABO_ERR_DIM;
     const size_t total = (size_t)gabo::chain_offset(D, levels);
     if (!x || !y || !axes_host || !distances_host || !out_host || !workspace || !pinned || !(beta > 0.0)) return GABO_ERR_ARG;
-    const gabo::SphereFitLayout lay(n, D, levels);
+    gabo::SphereFitLayout lay(n, D, levels, 0);
     if (workspace_bytes < lay.total || pinned_doubles < 2 * total + levels + 7) return GABO_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    char* base = static_cast<char*>(workspace);
-    auto at = [base](size_t off) { return reinterpret_cast<double*>(base + off); };
-    double* d_axes = at(lay.axes);             // [axes (total) | distances (levels)]
-    double* d_dists = d_axes + total;
-    double* d_out = at(lay.out);
-    int* counter = reinterpret_cast<int*>(base + lay.counters);
-    std::memcpy(pinned, axes_host, sizeof(double) * total);
-    std::memcpy(pinned + total, distances_host, sizeof(double) * levels);
-    if (hipMemcpyAsync(d_axes, pinned, sizeof(double) * (total + levels), hipMemcpyHostToDevice, s) != hipSuccess) return GABO_ERR_LAUNCH;
-    hipLaunchKernelGGL(gabo::nested_sphere_frames_kernel, dim3((unsigned)levels), dim3(64), 0, s, d_axes, at(lay.frames), D, levels);
-    const size_t nfr = ((size_t)gabo::chain_offset(D, levels) + 2 * (size_t)levels);
-    const size_t lds_fwd = (size_t)(D + levels) * sizeof(double), lds_bwd = ((size_t)(2 * D + levels) + nfr) * sizeof(double);
-    if (!gabo::chain_lds_ok(gabo::nested_sphere_project_backward_kernel, lds_bwd)) return GABO_ERR_DIM;
-    hipLaunchKernelGGL(gabo::nested_sphere_project_kernel, dim3((unsigned)n), dim3(64), lds_fwd, s, x, at(lay.frames), d_dists,
-                       at(lay.z), want_grad ? at(lay.store) : nullptr, D, levels);
-    if (hipGetLastError() != hipSuccess) return GABO_ERR_LAUNCH;
-    int rc = gabo_sphere_pairwise(at(lay.z), at(lay.z), at(lay.kb), 1, n, n, lat, 0, 0, beta, GABO_OUT_GAUSSIAN, 0, stream);
-    if (rc != GABO_OK) return rc;
-    double* wm = want_grad ? at(lay.wm) : nullptr;
-    if (n <= GABO_GP_MLL_MAX_N)
-        rc = gabo_gp_mll_gram(at(lay.kb), y, n, outputscale, noise, mean, d_out, wm, stream);
-    else
-        rc = gabo_gp_mll_large(at(lay.kb), y, n, 0.0, outputscale, noise, mean, 1, d_out, wm, base + lay.mll, gabo_gp_mll_large_workspace_bytes(n), stream);
-    if (rc != GABO_OK) return rc;
-    size_t out_doubles = 6;
-    if (want_grad) {
-        if (hipMemsetAsync(counter, 0, sizeof(int), s) != hipSuccess) return GABO_ERR_LAUNCH;
-        rc = gabo::fit_gram_adjoint_launch(at(lay.kb), wm, at(lay.gs), d_out, at(lay.partial), counter, n, 0.5 * outputscale, beta, lay.blocks_gram, s);
-        if (rc != GABO_OK) return rc;
-        hipLaunchKernelGGL(gabo::sphere_gram_adjoint_kernel, dim3((unsigned)n), dim3(64), (size_t)(65 * lat) * sizeof(double), s, at(lay.z), at(lay.gs),
-                           at(lay.gz), (int)n, lat, beta);
-        hipLaunchKernelGGL(gabo::nested_sphere_project_backward_kernel, dim3((unsigned)n), dim3(64), lds_bwd, s, at(lay.store),
-                           at(lay.frames), d_dists, at(lay.gz), at(lay.partial), D, levels);
-        hipLaunchKernelGGL(gabo::nested_sphere_axes_adjoint_kernel, dim3((unsigned)levels), dim3(64), (size_t)D * sizeof(double), s, d_axes, at(lay.frames),
-                           at(lay.partial), d_out + 7, (int)n, D, levels);
-        if (hipGetLastError() != hipSuccess) return GABO_ERR_LAUNCH;
-        out_doubles = 7 + total;
-    }
-    double* h_out = pinned + total + levels;
-    if (hipMemcpyAsync(h_out, d_out, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, s) != hipSuccess) return GABO_ERR_LAUNCH;
-    if (hipStreamSynchronize(s) != hipSuccess) return GABO_ERR_LAUNCH;
-    std::memcpy(out_host, h_out, sizeof(double) * out_doubles);
-    if (!want_grad) {
-        out_host[6] = 0.0;
-        std::memset(out_host + 7, 0, sizeof(double) * total);
-    }
-    return GABO_OK;
+    return gabo::sphere_fit_chain(
+        lay, x, y, axes_host, distances_host, n, D, levels, outputscale, noise, mean, want_grad, out_host, workspace, pinned, sizeof(int), stream,
+        [&] { return gabo_sphere_pairwise(lay.at(lay.z), lay.at(lay.z), lay.at(lay.kb), 1, n, n, lat, 0, 0, beta, GABO_OUT_GAUSSIAN, 0, stream); },
+        [&](double* wm, double* d_out, int* counter) {
+            const int rc = gabo::fit_gram_adjoint_launch(lay.at(lay.kb), wm, lay.at(lay.gs), d_out, lay.at(lay.partial), counter, n, 0.5 * outputscale,
+                                                         beta, lay.blocks_gram, s);
+            if (rc != GABO_OK) return rc;
+            hipLaunchKernelGGL(gabo::sphere_gram_adjoint_kernel, dim3((unsigned)n), dim3(64), (size_t)(65 * lat) * sizeof(double), s, lay.at(lay.z),
+                               lay.at(lay.gs), lay.at(lay.gz), (int)n, lat, beta);
+            return (int)GABO_OK;
+        });
 }
 
 size_t gabo_nested_sphere_fit_series_workspace_bytes(int64_t n, int D, int levels, int n_coeff) {
     if (n < 1 || D < 2 || levels < 1 || levels > D - 1 || n_coeff < 1 || n_coeff > gabo::kZonalMaxCoeff) return 0;
-    return gabo::SphereSeriesFitLayout(n, D, levels, n_coeff).total;
+    return gabo::SphereFitLayout(n, D, levels, n_coeff).total;
 }
 
 int gabo_nested_sphere_fit_evaluate_series(const double* x, const double* y, const double* axes_host, const double* distances_host, int64_t n,
@@ -660,70 +654,23 @@ int gabo_nested_sphere_fit_evaluate_series(const double* x, const double* y, con
     const size_t total = (size_t)gabo::chain_offset(D, levels);
     if (!x || !y || !axes_host || !distances_host || !coeff_host || !dcoeff_host || !out_host || !workspace || !pinned) return GABO_ERR_ARG;
     if (n_coeff < 1 || n_coeff > gabo::kZonalMaxCoeff) return GABO_ERR_ARG;
-    const gabo::SphereSeriesFitLayout lay(n, D, levels, n_coeff);
-    const size_t upload = lay.table_at + 4 * (size_t)n_coeff;
-    if (workspace_bytes < lay.total || pinned_doubles < upload + 7 + total) return GABO_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    char* base = static_cast<char*>(workspace);
-    auto at = [base](size_t off) { return reinterpret_cast<double*>(base + off); };
-    double* d_axes = at(lay.axes);             // [axes (total) | distances (levels) | pad | table (2 x n_coeff pairs)]
-    double* d_dists = d_axes + total;
-    double* d_table = d_axes + lay.table_at;
-    double* d_out = at(lay.out);
-    int* counter = reinterpret_cast<int*>(base + lay.counters);
-    std::memcpy(pinned, axes_host, sizeof(double) * total);
-    std::memcpy(pinned + total, distances_host, sizeof(double) * levels);
-    {
-        // row 0: f' = sum_{k >= 1} p_k k (k + d - 1) / d P_{k-1}^(d+2)  (ops._zonal_derivative, operation for operation), zero-padded to n_coeff
-        // levels; row 1: d f / d kappa in dimension d.  B_k = (k - 1) / (k + dimension - 2), B_0 = B_1 = 0 (zonal_series of sphere_zonal.hip)
-        double* t0 = pinned + lay.table_at;
-        double* t1 = t0 + 2 * (size_t)n_coeff;
-        if (lay.table_at > total + levels) pinned[total + levels] = 0.0;
-        for (int k = 0; k < n_coeff; ++k) {
-            const double kk = (double)(k + 1);
-            t0[2 * k] = k + 1 < n_coeff ? coeff_host[k + 1] * (kk * (kk + ((double)sd - 1.0))) / (double)sd : 0.0;
-            t0[2 * k + 1] = k >= 2 ? ((double)k - 1.0) / ((double)k + (double)(sd + 2) - 2.0) : 0.0;
-            t1[2 * k] = dcoeff_host[k];
-            t1[2 * k + 1] = k >= 2 ? ((double)k - 1.0) / ((double)k + (double)sd - 2.0) : 0.0;
-        }
-    }
-    if (hipMemcpyAsync(d_axes, pinned, sizeof(double) * upload, hipMemcpyHostToDevice, s) != hipSuccess) return GABO_ERR_LAUNCH;
-    hipLaunchKernelGGL(gabo::nested_sphere_frames_kernel, dim3((unsigned)levels), dim3(64), 0, s, d_axes, at(lay.frames), D, levels);
-    const size_t nfr = total + 2 * (size_t)levels;
-    const size_t lds_fwd = (size_t)(D + levels) * sizeof(double), lds_bwd = ((size_t)(2 * D + levels) + nfr) * sizeof(double);
-    if (!gabo::chain_lds_ok(gabo::nested_sphere_project_backward_kernel, lds_bwd)) return GABO_ERR_DIM;
-    hipLaunchKernelGGL(gabo::nested_sphere_project_kernel, dim3((unsigned)n), dim3(64), lds_fwd, s, x, at(lay.frames), d_dists,
-                       at(lay.z), want_grad ? at(lay.store) : nullptr, D, levels);
-    if (hipGetLastError() != hipSuccess) return GABO_ERR_LAUNCH;
-    int rc = gabo_sphere_zonal_pairwise(at(lay.z), at(lay.z), at(lay.kb), 1, n, n, lat, 0, 0, coeff_host, n_coeff, sd, GABO_SYMMETRIC, 0, stream);
-    if (rc != GABO_OK) return rc;
-    double* wm = want_grad ? at(lay.wm) : nullptr;
-    if (n <= GABO_GP_MLL_MAX_N)
-        rc = gabo_gp_mll_gram(at(lay.kb), y, n, outputscale, noise, mean, d_out, wm, stream);
-    else
-        rc = gabo_gp_mll_large(at(lay.kb), y, n, 0.0, outputscale, noise, mean, 1, d_out, wm, base + lay.mll, gabo_gp_mll_large_workspace_bytes(n), stream);
-    if (rc != GABO_OK) return rc;
-    size_t out_doubles = 6;
-    if (want_grad) {
-        if (hipMemsetAsync(counter, 0, 2 * sizeof(double), s) != hipSuccess) return GABO_ERR_LAUNCH;
-        hipLaunchKernelGGL(gabo::nested_sphere_zonal_adjoint_kernel, dim3((unsigned)n), dim3(64), (size_t)(65 * lat + 66) * sizeof(double), s, at(lay.z),
-                           wm, d_table, at(lay.gz), at(lay.kappa), counter, d_out, (int)n, lat, n_coeff, 0.5 * outputscale);
-        hipLaunchKernelGGL(gabo::nested_sphere_project_backward_kernel, dim3((unsigned)n), dim3(64), lds_bwd, s, at(lay.store),
-                           at(lay.frames), d_dists, at(lay.gz), at(lay.partial), D, levels);
-        hipLaunchKernelGGL(gabo::nested_sphere_axes_adjoint_kernel, dim3((unsigned)levels), dim3(64), (size_t)D * sizeof(double), s, d_axes, at(lay.frames),
-                           at(lay.partial), d_out + 7, (int)n, D, levels);
-        if (hipGetLastError() != hipSuccess) return GABO_ERR_LAUNCH;
-        out_doubles = 7 + total;
-    }
-    double* h_out = pinned + upload;
-    if (hipMemcpyAsync(h_out, d_out, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, s) != hipSuccess) return GABO_ERR_LAUNCH;
-    if (hipStreamSynchronize(s) != hipSuccess) return GABO_ERR_LAUNCH;
-    std::memcpy(out_host, h_out, sizeof(double) * out_doubles);
-    if (!want_grad) {
-        out_host[6] = 0.0;
-        std::memset(out_host + 7, 0, sizeof(double) * total);
-    }
-    return GABO_OK;
+    gabo::SphereFitLayout lay(n, D, levels, n_coeff);
+    if (workspace_bytes < lay.total || pinned_doubles < lay.upload + 7 + total) return GABO_ERR_ARG;
+    if (lay.table_at > total + levels) pinned[total + levels] = 0.0;
+    gabo::sphere_series_adjoint_table(pinned + lay.table_at, coeff_host, dcoeff_host, n_coeff, sd);
+    return gabo::sphere_fit_chain(
+        lay, x, y, axes_host, distances_host, n, D, levels, outputscale, noise, mean, want_grad, out_host, workspace, pinned, 2 * sizeof(double),
+        stream,
+        [&] {
+            return gabo_sphere_zonal_pairwise(lay.at(lay.z), lay.at(lay.z), lay.at(lay.kb), 1, n, n, lat, 0, 0, coeff_host, n_coeff, sd, GABO_SYMMETRIC, 0,
+                                              stream);
+        },
+        [&](double* wm, double* d_out, int* counter) {      // (checked with the launches behind it)
+            hipLaunchKernelGGL(gabo::nested_sphere_zonal_adjoint_kernel, dim3((unsigned)n), dim3(64), (size_t)(65 * lat + 66) * sizeof(double),
+                               (hipStream_t)stream, lay.at(lay.z), wm, lay.at(lay.axes) + lay.table_at, lay.at(lay.gz), lay.at(lay.kappa), counter,
+                               d_out, (int)n, lat, n_coeff, 0.5 * outputscale);
+            return (int)GABO_OK;
+        });
 }
 
 }  // extern "C"

@@ -52,14 +52,75 @@ class _MllProblem:
         return self.manifold.egrad2rgrad(x, self.egrad(x))
 
 
-class _NestedSpdMllProblem(_MllProblem):
+class _OneCallMllProblem(_MllProblem):
+    """The same objective without an autograd graph, for a kernel whose whole evaluation - Gram matrix, likelihood and their adjoints back to
+    the manifold-valued parameter - is ONE host call (a gabo_nested_*_fit_evaluate entry: one pinned copy in, one out): the chain rule through
+    softplus and the Gamma priors of the scalar hyper-parameters is Python float arithmetic (SingleTaskGP._fast_scalar_objective, whose
+    evaluator is `_one_call`).  A subclass sets `point` (the host array the entry reads: it keys the cache) in `_set_point`, names its buffer
+    sizes in `_sizes`, makes its ctypes call in `_call` (-> status, entry name) and hands the gradient tail back to the factors in `_scatter`."""
+
+    def _setup(self, model, ops):
+        self.ops = ops
+        dev = ops._device_for(model.train_x)
+        self.x = model.train_x.to(dev).double().contiguous()
+        self.y = model.train_y.to(dev).double().contiguous()
+        self.want_grad, self.values_only, self.point, self.tail, self._buffers, self._recent = False, False, None, None, None, []
+
+    def _one_call(self, theta, outputscale, noise, mean):
+        """One entry call - with the gradient unless only values are wanted (`values_only`): a line search asks for the value at a point and
+        the solver for the gradient at the point it accepted, so the last results are remembered and that second request costs nothing."""
+        import ctypes
+        from .. import _lib
+        lib = _lib.load()
+        if self._buffers is None:
+            ws_bytes, pinned_doubles, tail = self._sizes(lib)
+            ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=self.x.device)
+            self._buffers = (ws, torch.empty(pinned_doubles, dtype=torch.float64).pin_memory(), np.empty(7 + tail))
+        ws, pinned, out = self._buffers
+        key = (self.point.tobytes(), theta, outputscale, noise, mean)
+        for k, res in self._recent:
+            if k == key and (res[2] or not self.want_grad):
+                self.tail = res[1]
+                return res[0]
+        want = self.want_grad or not self.values_only
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        with torch.cuda.device(self.x.device):
+            _lib.check(*self._call(lib, ptr, float(theta), float(outputscale), float(noise), float(mean), 1 if want else 0, ptr(out), ws.data_ptr(),
+                                   ws.numel(), pinned.data_ptr(), pinned.numel(), self.ops._stream_ptr(self.x.device)))
+        res = ((float(out[0]), float(out[6]), float(out[2]), float(out[3]), float(out[4]), float(out[5])), out[7:].copy(), want)
+        self._recent = [(key, res)] + self._recent[:3]
+        self.tail = res[1]
+        return res[0]
+
+    def _run(self, x, want_grad):
+        self._set_point(x)
+        self.want_grad = want_grad
+        v = np.array([float(np.asarray(x[k]).reshape(-1)[0]) for k in self.scalar_idx])
+        return self.scalar(v)
+
+    def cost(self, x, run=None):
+        self.n_evals += 1
+        loss, _ = (run or self._run)(x, False)
+        return float("inf") if loss >= 1e10 else float(loss)
+
+    def egrad(self, x):
+        loss, g = self._run(x, True)
+        out = [None] * len(self.params)
+        for pos, k in enumerate(self.scalar_idx):
+            out[k] = np.full(np.shape(x[k]), g[pos])
+        self._scatter(out, x, None if loss >= 1e10 else -self.tail / self.y.numel())      # (None: zeros at the barrier value)
+        return out
+
+
+class _NestedSpdMllProblem(_OneCallMllProblem):
     """The same objective for ScaleKernel(NestedSpd{LogEuclidean, AffineInvariant}GaussianKernel) - the surrogate of HD-GaBO
     (examples/hd_bo_spd/benchmark_examples/hd_gabo_spd.py:163-205) - without an autograd graph: an evaluation is the chain
         project (gabo_spd_project) -> [logm (gabo_spd_logm_mandel)] -> Gaussian Gram of the latent points -> gabo_gp_mll_gram
     and, for the gradient, the kernels' own backward launches in reverse (W = alpha alpha^T - Ky^-1 from the likelihood launch is
-    d ll / d Gram up to outputscale / 2), the projection's adjoint dW = 2 sum_n X_n W G_n, and one read-back; the chain rule through
-    softplus and the Gamma priors of the scalar hyper-parameters is Python float arithmetic (SingleTaskGP._fast_scalar_objective).
-    Round 2 differentiated the same launches through torch autograd: 0.3 ms per value, 1.0 ms per gradient at n = 10."""
+    d ll / d Gram up to outputscale / 2), the projection's adjoint dW = 2 sum_n X_n W G_n, and one read-back.  The log-Euclidean kernel's chain
+    is one host call (gabo_nested_spd_fit_evaluate: the same launches issued from C++); `native = False` and the affine-invariant kernel issue
+    it launch by launch (`_evaluate`).  Round 2 differentiated the same launches through torch autograd: 0.3 ms per value, 1.0 ms per gradient
+    at n = 10."""
 
     @staticmethod
     def build(model, names, params, manifold):
@@ -82,51 +143,26 @@ class _NestedSpdMllProblem(_MllProblem):
         if any(params[k].numel() != 1 for k in self.scalar_idx):
             return None
         self.log_euclidean = type(base) is kspd.NestedSpdLogEuclideanGaussianKernel
-        self.ops = ops
-        dev = ops._device_for(model.train_x)
-        self.x = model.train_x.to(dev).double().contiguous()
+        self._setup(model, ops)
         self.xm = ops.mandel_to_matrix(self.x)                          # n x D x D, fixed during the fit (projection adjoint)
-        self.y = model.train_y.to(dev).double().contiguous()
-        self.W = None
-        self.want_grad = False
-        self.grad_w = None
-        self.native, self.values_only, self.W_host, self._native_buffers, self._recent = True, False, None, None, []
+        self.W, self.native = None, True
         self.scalar = model._fast_scalar_objective([params[k] for k in self.scalar_idx], evaluator=self._evaluate)
         return self if self.scalar is not None else None
 
-    def _native(self, theta, outputscale, noise, mean):
-        """The log-Euclidean kernel's chain as ONE host call (gabo_nested_spd_fit_evaluate: the same launches issued from C++, one pinned
-        copy in and one out) - always with the gradient: a line search asks for the value at a point and the solver for the gradient at the
-        point it accepted, so the last results are remembered and that second request costs nothing."""
-        import ctypes
-        from .. import _lib
-        lib = _lib.load()
-        n, D, d = self.x.shape[0], self.W_host.shape[0], self.W_host.shape[1]
-        if self._native_buffers is None:
-            ws = torch.empty(max(int(lib.gabo_nested_spd_fit_workspace_bytes(n, D, d)), 16), dtype=torch.uint8, device=self.x.device)
-            self._native_buffers = (ws, torch.empty(2 * D * d + 7, dtype=torch.float64).pin_memory(), np.empty(7 + D * d))
-        ws, pinned, out = self._native_buffers
-        key = (self.W_host.tobytes(), theta, outputscale, noise, mean)
-        for k, res in self._recent:
-            if k == key and (res[2] or not self.want_grad):
-                self.grad_w = res[1]
-                return res[0]
-        want = self.want_grad or not self.values_only
-        with torch.cuda.device(self.x.device):
-            _lib.check(lib.gabo_nested_spd_fit_evaluate(
-                self.x.data_ptr(), self.xm.data_ptr(), self.y.data_ptr(), self.W_host.ctypes.data_as(ctypes.c_void_p), n, D, d, float(theta),
-                float(outputscale), float(noise), float(mean), 1 if want else 0, out.ctypes.data_as(ctypes.c_void_p), ws.data_ptr(), ws.numel(),
-                pinned.data_ptr(), pinned.numel(), self.ops._stream_ptr(self.x.device)), "gabo_nested_spd_fit_evaluate")
-        res = ((float(out[0]), float(out[6]), float(out[2]), float(out[3]), float(out[4]), float(out[5])), out[7:].reshape(D, d).copy(), want)
-        self._recent = [(key, res)] + self._recent[:3]
-        self.grad_w = res[1]
-        return res[0]
+    def _sizes(self, lib):
+        D, d = self.point.shape
+        return lib.gabo_nested_spd_fit_workspace_bytes(self.x.shape[0], D, d), 2 * D * d + 7, D * d
+
+    def _call(self, lib, ptr, theta, outputscale, noise, mean, want, *buffers):
+        return lib.gabo_nested_spd_fit_evaluate(self.x.data_ptr(), self.xm.data_ptr(), self.y.data_ptr(), ptr(self.point), self.x.shape[0],
+                                                self.point.shape[0], self.point.shape[1], theta, outputscale, noise, mean, want,
+                                                *buffers), "gabo_nested_spd_fit_evaluate"
 
     def _evaluate(self, theta, outputscale, noise, mean):
         from .. import _lib
         ops = self.ops
         if self.log_euclidean and self.native:
-            return self._native(theta, outputscale, noise, mean)
+            return self._one_call(theta, outputscale, noise, mean)
         z = ops.spd_project(self.x, self.W)
         if self.log_euclidean:
             feat = ops.spd_logm_mandel(z)
@@ -148,34 +184,20 @@ class _NestedSpdMllProblem(_MllProblem):
         gm = ops.mandel_to_matrix(gz)                                    # n x d x d (symmetric)
         gw = 2.0 * torch.einsum("nab,bc,ncd->ad", self.xm, self.W, gm)
         flat = torch.cat([out, g_theta.reshape(1), gw.reshape(-1)]).tolist()          # one read-back
-        self.grad_w = np.asarray(flat[7:]).reshape(self.W.shape)
+        self.tail = np.asarray(flat[7:])
         return flat[0], flat[6], flat[2], flat[3], flat[4], flat[5]
 
-    def _run(self, x, want_grad):
+    def _set_point(self, x):
         if self.log_euclidean and self.native:
-            self.W_host = np.ascontiguousarray(np.asarray(x[self.iw], dtype=np.float64).reshape(self.params[self.iw].shape))
+            self.point = np.ascontiguousarray(np.asarray(x[self.iw], dtype=np.float64).reshape(self.params[self.iw].shape))
         else:
             self.W = torch.as_tensor(np.asarray(x[self.iw], dtype=np.float64), device=self.x.device).reshape(self.params[self.iw].shape).contiguous()
-        self.want_grad = want_grad
-        v = np.array([float(np.asarray(x[k]).reshape(-1)[0]) for k in self.scalar_idx])
-        return self.scalar(v)
 
-    def cost(self, x):
-        self.n_evals += 1
-        loss, _ = self._run(x, False)
-        return float("inf") if loss >= 1e10 else float(loss)
-
-    def egrad(self, x):
-        loss, g = self._run(x, True)
-        n = self.y.numel()
-        out = [None] * len(self.params)
-        for pos, k in enumerate(self.scalar_idx):
-            out[k] = np.full(np.shape(x[k]), g[pos])
-        out[self.iw] = (np.zeros(np.shape(x[self.iw])) if loss >= 1e10 else -self.grad_w.reshape(np.shape(x[self.iw])) / n)
-        return out
+    def _scatter(self, out, x, g):
+        out[self.iw] = np.zeros(np.shape(x[self.iw])) if g is None else g.reshape(np.shape(x[self.iw]))
 
 
-class _NestedSphereMllProblem(_MllProblem):
+class _NestedSphereMllProblem(_OneCallMllProblem):
     """The same objective for ScaleKernel(NestedSphereGaussianKernel) - the surrogate of HD-GaBO on the sphere
     (examples/hd_bo_sphere/benchmark_examples/hd_gabo_sphere.py:150-180): the axes of the nested spheres are learnt on their spheres together
     with the scalar hyper-parameters.  One evaluation is ONE host call (gabo_nested_sphere_fit_evaluate: every level of the projection for
@@ -208,70 +230,48 @@ class _NestedSphereMllProblem(_MllProblem):
         self.scalar_idx = [k for k in range(len(params)) if k not in axis_idx]
         if any(params[k].numel() != 1 for k in self.scalar_idx) or base.dim - base.latent_dim != len(axis_idx) or base.latent_dim > 64:
             return None
-        self.ops = ops
-        dev = ops._device_for(model.train_x)
-        self.x = model.train_x.to(dev).double().contiguous()
-        self.y = model.train_y.to(dev).double().contiguous()
+        self._setup(model, ops)
         if self.x.dim() != 2 or self.x.shape[1] != base.dim:
             return None
         self.D, self.L = int(base.dim), len(axis_idx)
         self.dists = np.array([float(d.reshape(-1)[0]) for d in base.distances_to_axis], dtype=np.float64)
         self.total = sum(self.D - k for k in range(self.L))
-        self.want_grad, self.values_only, self.axes_host, self.grad_axes, self._buffers, self._recent = False, False, None, None, None, []
         self.series = None
         if type(base) is NestedSphereRiemannianMaternKernel:
             if base.raw_lengthscale.numel() != 1:
                 return None
             self.series = (int(base.latent_dim), float(base.nu), int(base.num_levels))
-            self.scalar = model._fast_scalar_objective([params[k] for k in self.scalar_idx], evaluator=self._evaluate, evaluator_takes_value=True)
+            self.scalar = model._fast_scalar_objective([params[k] for k in self.scalar_idx], evaluator=self._one_call, evaluator_takes_value=True)
         else:
-            self.scalar = model._fast_scalar_objective([params[k] for k in self.scalar_idx], evaluator=self._evaluate)
+            self.scalar = model._fast_scalar_objective([params[k] for k in self.scalar_idx], evaluator=self._one_call)
         return self if self.scalar is not None else None
 
-    def _evaluate(self, theta, outputscale, noise, mean):
-        import ctypes
-        from .. import _lib
-        lib = _lib.load()
+    def _sizes(self, lib):
         n = self.x.shape[0]
-        if self._buffers is None:
-            if self.series is None:
-                ws_bytes, pinned_doubles = lib.gabo_nested_sphere_fit_workspace_bytes(n, self.D, self.L), 2 * self.total + self.L + 7
-            else:                           # (num_levels + 1 coefficients; the pinned buffer also carries the two series of the adjoint)
-                n_coeff = self.series[2] + 1
-                ws_bytes = lib.gabo_nested_sphere_fit_series_workspace_bytes(n, self.D, self.L, n_coeff)
-                pinned_doubles = 2 * self.total + self.L + 1 + 4 * n_coeff + 7
-            ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=self.x.device)
-            self._buffers = (ws, torch.empty(pinned_doubles, dtype=torch.float64).pin_memory(), np.empty(7 + self.total))
-        ws, pinned, out = self._buffers
-        key = (self.axes_host.tobytes(), theta, outputscale, noise, mean)
-        for k, res in self._recent:
-            if k == key and (res[2] or not self.want_grad):
-                self.grad_axes = res[1]
-                return res[0]
-        want = self.want_grad or not self.values_only
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
-        with torch.cuda.device(self.x.device):
-            if self.series is None:
-                _lib.check(lib.gabo_nested_sphere_fit_evaluate(
-                    self.x.data_ptr(), self.y.data_ptr(), ptr(self.axes_host), ptr(self.dists), n, self.D, self.L, float(theta), float(outputscale),
-                    float(noise), float(mean), 1 if want else 0, ptr(out), ws.data_ptr(), ws.numel(), pinned.data_ptr(), pinned.numel(),
-                    self.ops._stream_ptr(self.x.device)), "gabo_nested_sphere_fit_evaluate")
-            else:                           # theta is the lengthscale kappa (evaluator_takes_value)
-                p, dp, _ = self.ops.sphere_matern_coefficients_and_derivative(self.series[0], float(theta), self.series[1], self.series[2])
-                _lib.check(lib.gabo_nested_sphere_fit_evaluate_series(
-                    self.x.data_ptr(), self.y.data_ptr(), ptr(self.axes_host), ptr(self.dists), n, self.D, self.L, ptr(p), ptr(dp), int(p.size),
-                    float(outputscale), float(noise), float(mean), 1 if want else 0, ptr(out), ws.data_ptr(), ws.numel(), pinned.data_ptr(),
-                    pinned.numel(), self.ops._stream_ptr(self.x.device)), "gabo_nested_sphere_fit_evaluate_series")
-        res = ((float(out[0]), float(out[6]), float(out[2]), float(out[3]), float(out[4]), float(out[5])), out[7:].copy(), want)
-        self._recent = [(key, res)] + self._recent[:3]
-        self.grad_axes = res[1]
-        return res[0]
+        if self.series is None:
+            return lib.gabo_nested_sphere_fit_workspace_bytes(n, self.D, self.L), 2 * self.total + self.L + 7, self.total
+        n_coeff = self.series[2] + 1        # (num_levels + 1 coefficients; the pinned buffer also carries the two series of the adjoint)
+        return (lib.gabo_nested_sphere_fit_series_workspace_bytes(n, self.D, self.L, n_coeff), 2 * self.total + self.L + 1 + 4 * n_coeff + 7,
+                self.total)
 
-    def _run(self, x, want_grad):
-        self.axes_host = np.ascontiguousarray(np.concatenate([np.asarray(x[k], dtype=np.float64).reshape(-1) for k in self.axis_idx]))
-        self.want_grad = want_grad
-        v = np.array([float(np.asarray(x[k]).reshape(-1)[0]) for k in self.scalar_idx])
-        return self.scalar(v)
+    def _call(self, lib, ptr, theta, outputscale, noise, mean, want, *buffers):
+        head = (self.x.data_ptr(), self.y.data_ptr(), ptr(self.point), ptr(self.dists), self.x.shape[0], self.D, self.L)
+        if self.series is None:
+            return lib.gabo_nested_sphere_fit_evaluate(*head, theta, outputscale, noise, mean, want, *buffers), "gabo_nested_sphere_fit_evaluate"
+        # theta is the lengthscale kappa (evaluator_takes_value)
+        p, dp, _ = self.ops.sphere_matern_coefficients_and_derivative(self.series[0], theta, self.series[1], self.series[2])
+        return (lib.gabo_nested_sphere_fit_evaluate_series(*head, ptr(p), ptr(dp), int(p.size), outputscale, noise, mean, want, *buffers),
+                "gabo_nested_sphere_fit_evaluate_series")
+
+    def _set_point(self, x):
+        self.point = np.ascontiguousarray(np.concatenate([np.asarray(x[k], dtype=np.float64).reshape(-1) for k in self.axis_idx]))
+
+    def _scatter(self, out, x, g):
+        off = 0
+        for level, k in enumerate(self.axis_idx):
+            d = self.D - level
+            out[k] = np.zeros(np.shape(x[k])) if g is None else g[off:off + d].reshape(np.shape(x[k]))
+            off += d
 
     # the same objective on ONE flat vector (the factors' entries one after the other, PackedEuclideanSpheres): no list of ~50 arrays is
     # taken apart and put together again around every evaluation
@@ -280,39 +280,19 @@ class _NestedSphereMllProblem(_MllProblem):
         self._scalar_pos = np.array([bounds[k] for k in self.scalar_idx])
 
     def _run_flat(self, v, want_grad):
-        self.axes_host = np.ascontiguousarray(v[self._axes_pos])
+        self.point = np.ascontiguousarray(v[self._axes_pos])
         self.want_grad = want_grad
         return self.scalar(v[self._scalar_pos])
 
     def cost_flat(self, v):
-        self.n_evals += 1
-        loss, _ = self._run_flat(v, False)
-        return float("inf") if loss >= 1e10 else float(loss)
+        return self.cost(v, self._run_flat)
 
     def egrad_flat(self, v):
         loss, g = self._run_flat(v, True)
         out = np.zeros(v.shape[0])
         out[self._scalar_pos] = g
         if loss < 1e10:
-            out[self._axes_pos] = -self.grad_axes / self.y.numel()
-        return out
-
-    def cost(self, x):
-        self.n_evals += 1
-        loss, _ = self._run(x, False)
-        return float("inf") if loss >= 1e10 else float(loss)
-
-    def egrad(self, x):
-        loss, g = self._run(x, True)
-        n = self.y.numel()
-        out = [None] * len(self.params)
-        for pos, k in enumerate(self.scalar_idx):
-            out[k] = np.full(np.shape(x[k]), g[pos])
-        off = 0
-        for level, k in enumerate(self.axis_idx):
-            d = self.D - level
-            out[k] = np.zeros(np.shape(x[k])) if loss >= 1e10 else (-self.grad_axes[off:off + d] / n).reshape(np.shape(x[k]))
-            off += d
+            out[self._axes_pos] = -self.tail / self.y.numel()
         return out
 
 
