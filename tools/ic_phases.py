@@ -1,4 +1,5 @@
-"""Host-side anatomy of gen_batch_initial_conditions_manifold in the config-4 sweep (development)."""
+"""Host-side anatomy of gen_batch_initial_conditions_manifold in the config-4 sweep (development).  The Python path of manifold_optimize.py: the
+native drivers (manifold_optimization/native_sweep.py) share its host sampler and retry loop but none of the functions wrapped here."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,8 +19,8 @@ mo.initialize_q_batch_nonneg = wrap("select", mo.initialize_q_batch_nonneg)
 mo.gen_batch_initial_conditions_manifold = wrap("initial_conditions", mo.gen_batch_initial_conditions_manifold)
 mo.FusedAcquisition.build = staticmethod(wrap("fused.build", mo.FusedAcquisition.build))
 for _ in range(3):
-    sweep_bench.run_sweep("cuda:0", builtin_constraint=True, device_rand=True)
+    sweep_bench.run_sweep("cuda:0", builtin_constraint=True, device_rand=True, native_sweep=False)
 for _ in range(3):
     T.clear()
-    dt, *_ = sweep_bench.run_sweep("cuda:0", builtin_constraint=True, device_rand=True)
+    dt, *_ = sweep_bench.run_sweep("cuda:0", builtin_constraint=True, device_rand=True, native_sweep=False)
     print("total %.2f ms" % (dt * 1e3), {k: round(v * 1e3, 3) for k, v in T.items()})

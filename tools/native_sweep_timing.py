@@ -1,4 +1,5 @@
-"""config-4 sweep, device-drawn raw samples: the native driver (gabo_spd_sweep_score / _solve) against the Python path (development)."""
+"""config-4 sweep, device-drawn raw samples: the native driver (manifold_optimization/native_sweep.py: _native_sweep over gabo_spd_sweep_score_rows /
+_select_rows / _solve_rows) against the Python path of manifold_optimize.py (development)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tools.sweep_bench import run_sweep

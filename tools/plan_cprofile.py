@@ -1,4 +1,4 @@
-"""cProfile of the per-GP set-up of a sweep (FusedAcquisition.build through _native_sweep_plan), development."""
+"""cProfile of the per-GP set-up of a sweep (FusedAcquisition.build, as manifold_optimization/native_sweep.py's _native_sweep_plan calls it), development."""
 import cProfile, os, pstats, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -1,3 +1,5 @@
+"""Host timeline of a native sweep's plan and C calls (development).  _native_sweep_plan lives in manifold_optimization/native_sweep.py;
+joint_optimize_manifold looks it up in manifold_optimize's globals, so it is wrapped there.  Both modules load the library through _lib.load."""
 import os, sys, time
 sys.path.insert(0, os.getcwd())
 import numpy as np, torch
@@ -26,7 +28,6 @@ class L:
             TL.append(("-> C " + n, time.perf_counter())); r = f(*a); TL.append(("<- C " + n, time.perf_counter())); return r
         return w
 ops._lib.load = lambda: L()
-mo_lib = L()
 kw = dict(num_restarts=64, raw_samples=256, device_rand=True, builtin_constraint=True)
 for _ in range(5):
     sweep_bench.run_sweep("cuda:0", **kw)
