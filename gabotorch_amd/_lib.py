@@ -128,6 +128,10 @@ SIGNATURES = {
     "gabo_gp_factor": (_I, [_P, _P, _I64, _D, _D, _D, _P, _P, _P, _P, _P, _P]),
     "gabo_gp_mll_large_workspace_bytes": (_SZ, [_I64]),
     "gabo_gp_mll_large": (_I, [_P, _P, _I64, _D, _D, _D, _D, _I, _P, _P, _P, _SZ, _P]),
+    "gabo_flat_matern_pairwise": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, _I64, _I64, _D, _I, _P]),
+    "gabo_flat_matern_backward": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _I64, _I64, _I64, _I64, _I64, _D, _I, _D, _P]),
+    "gabo_flat_matern_from_distance": (_I, [_P, _P, _I64, _D, _I, _I, _P]),
+    "gabo_gp_mll_matern": (_I, [_P, _P, _I64, _D, _I, _D, _D, _D, _P, _P]),
     "gabo_gram_extreme_eig_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "gabo_gram_extreme_eig": (_I, [_P, _I64, _I64, _P, _I64, _P, _P, _SZ, _P]),
     "gabo_gp_posterior_joint_workspace_bytes": (_SZ, [_I64, _I64]),

@@ -32,10 +32,13 @@ def _surrogate_view(gp):
 
 
 class FusedAcquisition:
-    def __init__(self, acq, family, mode, beta, matrix_input, device, flavour="ai", view=None, zonal=None):
+    def __init__(self, acq, family, mode, beta, matrix_input, device, flavour="ai", view=None, zonal=None, matern=None):
         base, outputscale, mean, (linv, alpha), train_x = view if view is not None else _surrogate_view(acq.model)
         self.family, self.mode, self.beta, self.matrix_input = family, mode, beta, matrix_input
         self.flavour = flavour          # SPD kernels: "ai" affine-invariant, "le" log-Euclidean, "frob" Frobenius
+        # flat SPD Matern kernel ("le" / "frob"): (lengthscale, nu); `mode` and `beta` are None - the object has no Gaussian form, only the
+        # separate-launch chain (`single_launch` stays false), and nothing may read it as one
+        self.matern = matern
         self.zonal = None               # sphere Matern / heat kernel: the host's series of f and f' (`beta` is the lengthscale, `mode` GABO_OUT_ZONAL under `series_launch`)
         self.kind = _lib.GABO_ACQ_EXPECTED_IMPROVEMENT if isinstance(acq, models.ExpectedImprovement) else _lib.GABO_ACQ_POSTERIOR_MEAN
         self.maximize = bool(acq.maximize)
@@ -94,7 +97,10 @@ class FusedAcquisition:
             self.kxx = 1.0
             self.train_feat = ops.spd_logm_mandel(self.train) if flavour == "le" else self.train
             d_spd = ops._mandel_dim(self.train.shape[-1])
-            if (d_spd <= 8 and self.train.shape[0] <= _lib.load().gabo_spd_acq_max_train(d_spd) and mode == _lib.GABO_OUT_GAUSSIAN):
+            if matern is not None:
+                # k(x, x) at r = ||0 + 1e-15||_F = d 1e-15, from the launch that forms the strips: the bits of the diagonal of kernel(x, x)
+                self.kxx = float(ops.flat_matern_pairwise(self.train_feat[:1], self.train_feat[:1], *matern)[0, 0])
+            elif (d_spd <= 8 and self.train.shape[0] <= _lib.load().gabo_spd_acq_max_train(d_spd) and mode == _lib.GABO_OUT_GAUSSIAN):
                 # one launch per evaluation for these too: the "factors" are the training features, entry-major
                 self.single_launch = True
                 self.train_factors = self.train_feat.t().contiguous()
@@ -154,6 +160,12 @@ class FusedAcquisition:
             ls = float(k.lengthscale.detach().double())
             flavour = "le" if type(k) is kernels_spd.SpdLogEuclideanGaussianKernel else "frob"
             return FusedAcquisition(acq, "spd", _lib.GABO_OUT_GAUSSIAN, 1.0 / (ls * ls), True, device, flavour=flavour)
+        if type(k) in (kernels_spd.SpdLogEuclideanMaternKernel, kernels_spd.SpdFrobeniusMaternKernel):
+            if post_processing is not spd_utils_torch.symmetric_matrix_to_vector_mandel_torch:
+                return None
+            flavour = "le" if type(k) is kernels_spd.SpdLogEuclideanMaternKernel else "frob"
+            return FusedAcquisition(acq, "spd", None, None, True, device, flavour=flavour, view=view,
+                                    matern=(float(k.lengthscale.detach().double()), k.nu))
         if type(k) in (kernels_sphere.SphereGaussianKernel, kernels_sphere.SphereLaplaceKernel):
             if post_processing is not None:
                 return None
@@ -169,6 +181,12 @@ class FusedAcquisition:
             return FusedAcquisition(acq, "sphere", None, float(k.lengthscale.double()), False, device, zonal=(k.nu, k.num_levels))
         return None
 
+    def _flat_strip(self, feat):
+        """K(X*, X_train) on the features of the log-Euclidean / Frobenius flavours: the Gaussian form, or the Matern launch"""
+        if self.matern is not None:
+            return ops.flat_matern_pairwise(feat, self.train_feat, *self.matern)
+        return ops.frobenius_pairwise(feat, self.train_feat, self.beta, self.mode)
+
     def _sphere_f(self, c, order):
         """f^(order) on the inner products c: the geodesic kernels' closed forms, or the series of the Matern / heat kernel"""
         if self.zonal is not None:
@@ -181,7 +199,7 @@ class FusedAcquisition:
             return pts, ops.spd_ai_pairwise(pts, self.train, self.beta, self.mode), None
         if self.family == "spd":
             feat = ops.spd_logm_mandel(pts) if self.flavour == "le" else pts
-            return pts, ops.frobenius_pairwise(feat, self.train_feat, self.beta, self.mode), feat
+            return pts, self._flat_strip(feat), feat
         c = pts @ self.train.t()
         return pts, self._sphere_f(c, 0), c
 
@@ -199,13 +217,16 @@ class FusedAcquisition:
         if self.flavour == "ai":
             return pts, ops.spd_ai_pairwise(pts, self.train, self.beta, self.mode), None
         feat = ops.spd_logm_mandel(pts) if self.flavour == "le" else pts
-        return pts, ops.frobenius_pairwise(feat, self.train_feat, self.beta, self.mode), feat
+        return pts, self._flat_strip(feat), feat
 
     def _strip_backward(self, pts, feat, gk):
         """d/d pts (Mandel) of sum(gk * strip)"""
         if self.flavour == "ai":
             return ops.spd_ai_backward(pts, self.train, gk, self.beta, self.mode, wrt=1)
-        g = ops.frobenius_backward(feat, self.train_feat, gk, self.beta, self.mode, wrt=1)
+        if self.matern is not None:
+            g = ops.flat_matern_backward(feat, self.train_feat, gk, *self.matern, wrt=1)
+        else:
+            g = ops.frobenius_backward(feat, self.train_feat, gk, self.beta, self.mode, wrt=1)
         return ops.spd_logm_mandel_backward(pts, g) if self.flavour == "le" else g
 
     def sphere_acq_params(self):
@@ -219,6 +240,8 @@ class FusedAcquisition:
 
     def acq_params(self):
         """The surrogate as the gabo_spd_acq_params struct of the C ABI (single-launch path only)."""
+        if self.matern is not None:
+            raise RuntimeError("the single-launch evaluators carry no Matern form: a flat SPD Matern surrogate runs the separate-launch chain")
         # (A for both factor slots when the model's cache holds it: one matrix-vector product per evaluation instead of two, csrc/spd_acq_body.hpp)
         la, lb = (self.kinv.data_ptr(), self.kinv.data_ptr()) if self.kinv is not None else (self.linv.data_ptr(), self.linv_t.data_ptr())
         return _lib.AcqParams(self.train_factors.data_ptr(), self.alpha.data_ptr(), la, lb,

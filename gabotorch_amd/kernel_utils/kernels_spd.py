@@ -113,6 +113,44 @@ class SpdLogEuclideanGaussianKernel(Kernel):
         return ops.frobenius_kernel(l1, l2, _beta_from_lengthscale(self.lengthscale), _lib.GABO_OUT_GAUSSIAN)
 
 
+class _FlatMaternKernel(Kernel):
+    """The Matern kernel of a flat SPD metric: the metric's feature map is an isometry into R^{d(d+1)/2}, so the Riemannian Matern kernel
+    is the Euclidean one of the distance r and is positive definite for every lengthscale (no beta_min, nothing for kernel_parameters to
+    find).  gpytorch's MaternKernel parametrisation, x = sqrt(2 nu) r / lengthscale:
+        k = exp(-x) | (1 + x) exp(-x) | (1 + x + x^2 / 3) exp(-x)     for nu = 0.5 | 1.5 | 2.5,
+    NOT the exp(-r^2 / lengthscale^2) convention of the Gaussian classes (their nu = infinity limit is exp(-r^2 / (2 lengthscale^2))).
+    nu is fixed, not a parameter.  Differentiable (first order) in x1, x2 and the lengthscale through the HIP backward."""
+
+    def __init__(self, nu=2.5, **kwargs):
+        if isinstance(nu, bool) or not isinstance(nu, (int, float)) or nu not in (0.5, 1.5, 2.5):
+            raise ValueError(f"nu must be 0.5, 1.5 or 2.5, got {nu!r}")
+        self.has_lengthscale = True
+        super().__init__(has_lengthscale=True, ard_num_dims=None, **kwargs)
+        self.nu = float(nu)
+
+    def _features(self, x):
+        return x
+
+    def forward(self, x1, x2, diagonal_distance=False, **params):
+        if diagonal_distance is True:
+            return _diag_ones(x2)
+        f1 = self._features(x1)
+        f2 = f1 if x2 is x1 else self._features(x2)
+        return ops.flat_matern_kernel(f1, f2, self.lengthscale.double().reshape(()), self.nu)
+
+
+class SpdFrobeniusMaternKernel(_FlatMaternKernel):
+    """Matern kernel (nu = 0.5, 1.5, 2.5) of the Frobenius distance ||X - Y + 1e-15||_F on Mandel inputs."""
+
+
+class SpdLogEuclideanMaternKernel(_FlatMaternKernel):
+    """Matern kernel (nu = 0.5, 1.5, 2.5) of the log-Euclidean distance ||logm X - logm Y + 1e-15||_F on Mandel inputs: O(N) matrix
+    logarithms, reused when x2 is x1, and one pairwise launch."""
+
+    def _features(self, x):
+        return ops.spd_logm_mandel_diff(x)
+
+
 def _beta_from_lengthscale(ls):
     # exp(-d^2 / l^2) = exp(-beta d^2) with beta = l^-2, kept in torch so the lengthscale stays differentiable for the GP fit
     ls = ls.double().reshape(())

@@ -552,10 +552,38 @@ class SingleTaskGP(torch.nn.Module):
         dim, nu, levels = x.shape[-1], base.nu, base.num_levels
         return c, (lambda kappa: ops.sphere_matern_coefficients_and_derivative(dim, kappa, nu, levels)), os_fn
 
+    def _matern_form(self):
+        """(R, lengthscale_fn, nu, outputscale_fn) when the covariance is [ScaleKernel of] SpdLogEuclideanMaternKernel / SpdFrobeniusMaternKernel:
+        a Matern function of the distance matrix R of the training features, which is fixed during a fit while the lengthscale moves
+        (ops.gp_mll_matern); None for anything else, a batched lengthscale or more than GABO_GP_MLL_LARGE_MAX_N points.  R is what the
+        GABO_OUT_DISTANCE launch writes on the features the kernel's forward forms."""
+        from . import _lib, ops
+        from .kernel_utils import kernels_spd as _ks
+        cm = self.covar_module
+        base = getattr(cm, "base_kernel", None)
+        if base is None:
+            base, os_fn = cm, (lambda: torch.ones((), dtype=torch.float64))
+        elif type(cm).__name__ == "ScaleKernel" and cm.raw_outputscale.numel() == 1:
+            os_fn = lambda: cm.outputscale.double().reshape(())                                # noqa: E731
+        else:
+            return None
+        x = self.train_x
+        if type(base) not in (_ks.SpdLogEuclideanMaternKernel, _ks.SpdFrobeniusMaternKernel) or x.dim() != 2 \
+                or not 1 <= x.shape[0] <= _lib.GABO_GP_MLL_LARGE_MAX_N:
+            return None
+        if base.raw_lengthscale.numel() != 1:
+            return None
+        with torch.no_grad():
+            xd = x.double().to(ops._device_for(x))
+            feat = ops.spd_logm_mandel(xd) if type(base) is _ks.SpdLogEuclideanMaternKernel else xd
+            r = ops.frobenius_pairwise(feat, feat, 1.0, _lib.GABO_OUT_DISTANCE).contiguous()
+        return r, (lambda: base.lengthscale.double().reshape(())), base.nu, os_fn
+
     def _fast_evaluator(self):
         """(launch(parameter, outputscale, noise, mean) -> the six numbers of ops.gp_mll, parameter_fn, outputscale_fn, series?) on the matrix
         that is fixed during a fit: the exponent matrix of a plain kernel (parameter theta), else the inner products of the sphere Matern
-        kernel (parameter: the lengthscale kappa itself); None when the model has neither form."""
+        kernel or the distances of a flat SPD Matern kernel (parameter: the lengthscale itself, `series`); None when the model has none of
+        the three forms."""
         from . import ops
         form = self._stationary_form()
         if form is not None:
@@ -564,7 +592,12 @@ class SingleTaskGP(torch.nn.Module):
             return (lambda theta, os_, noise, mean: ops.gp_mll(e, y, theta, os_, noise, mean)), theta_fn, os_fn, False
         form = self._series_form()
         if form is None:
-            return None
+            form = self._matern_form()
+            if form is None:
+                return None
+            r, ls_fn, nu, os_fn = form
+            y = self.train_y.to(r.device).contiguous()
+            return (lambda ls, os_, noise, mean: ops.gp_mll_matern(r, y, ls, nu, os_, noise, mean)), ls_fn, os_fn, True
         c, coeff_fn, os_fn = form
         y = self.train_y.to(c.device).contiguous()
         base = getattr(self.covar_module, "base_kernel", self.covar_module)

@@ -1236,6 +1236,141 @@ def frobenius_kernel(x1, x2, beta, mode=_lib.GABO_OUT_GAUSSIAN):
     return _FrobeniusKernelFunction.apply(x1, x2, beta, int(mode))
 
 
+# ---- Matern kernels on the flat SPD metrics (csrc/flat_matern.hip): features are Mandel vectors, the distance is frobenius_pairwise's ----
+def _matern_nu2(nu):
+    """2 nu for nu in {0.5, 1.5, 2.5} (ValueError otherwise): the smoothness the C entries take"""
+    try:
+        nu2 = int(round(2.0 * float(nu)))
+    except (TypeError, ValueError, OverflowError):
+        nu2 = -1
+    if nu2 not in (1, 3, 5) or float(nu) * 2.0 != nu2:
+        raise ValueError(f"nu must be 0.5, 1.5 or 2.5, got {nu!r}")
+    return nu2
+
+
+def _matern_lengthscale(lengthscale):
+    """the lengthscale as a positive finite Python float (ValueError otherwise), as the C entries check it"""
+    import math
+    if torch.is_tensor(lengthscale) and lengthscale.numel() != 1:
+        raise RuntimeError("gabotorch_amd SPD kernels take a single lengthscale (batch_shape == ())")
+    value = float(lengthscale)
+    if not (value > 0.0 and math.isfinite(value)):
+        raise ValueError(f"the lengthscale must be positive and finite, got {value!r}")
+    return value
+
+
+def flat_matern_pairwise(x1, x2, lengthscale, nu):
+    """Mandel vectors x1 (..., N1, d_vec), x2 (..., N2, d_vec) -> (..., N1, N2) Matern kernel k_nu(r; lengthscale) of the distance r of
+    frobenius_pairwise, nu in {0.5, 1.5, 2.5}, in gpytorch's MaternKernel parametrisation (x = sqrt(2 nu) r / lengthscale).  With
+    `x2 is x1` the matrix is symmetric to the last bit."""
+    lib = _lib.load()
+    nu2, lval = _matern_nu2(nu), _matern_lengthscale(lengthscale)
+    if x1.shape[:-2] != x2.shape[:-2] or x1.shape[-1] != x2.shape[-1]:
+        raise RuntimeError(f"batch/feature shapes differ: {tuple(x1.shape)} vs {tuple(x2.shape)}")
+    out_device = x1.device
+    dev = _device_for(x1, x2)
+    a, b = _prep(x1, dev), _prep(x2, dev)
+    d = _mandel_dim(a.shape[-1])
+    n1, n2 = a.shape[-2], b.shape[-2]
+    a2, nb, s1 = _flatten_batch(a, 2)
+    b2, _, s2 = (a2, nb, s1) if x2 is x1 else _flatten_batch(b, 2)      # (one point set: the same pointer, and with it an exactly symmetric matrix)
+    out = torch.empty(a.shape[:-2] + (n1, n2), dtype=torch.float64, device=dev)
+    with _on(dev):
+        _lib.check(lib.gabo_flat_matern_pairwise(a2.data_ptr(), b2.data_ptr(), out.data_ptr(), nb, n1, n2, d, s1, s2, lval, nu2,
+                                                 _stream_ptr(dev)), "gabo_flat_matern_pairwise")
+    return _out(out, out_device)
+
+
+def flat_matern_backward(x1, x2, grad_out, lengthscale, nu, wrt=1):
+    """Gradient of sum(grad_out * flat_matern_pairwise(x1, x2)) with respect to x1 (wrt=1) or x2 (wrt=2); grad_out may be strided."""
+    lib = _lib.load()
+    nu2, lval = _matern_nu2(nu), _matern_lengthscale(lengthscale)
+    if wrt not in (1, 2):
+        raise ValueError(f"wrt must be 1 or 2, got {wrt!r}")
+    out_device = (x1 if wrt == 1 else x2).device
+    dev = _device_for(x1, x2, grad_out)
+    a, b, g = _prep(x1, dev), _prep(x2, dev), _prep(grad_out, dev)
+    d = _mandel_dim(a.shape[-1])
+    n1, n2 = a.shape[-2], b.shape[-2]
+    bshape = a.shape[:-2]
+    a2, nb, s1 = _flatten_batch(a, 2)
+    b2, _, s2 = _flatten_batch(b, 2)
+    if g.dim() == 2 and tuple(g.shape) == (n1, n2) and nb == 1 and min(g.stride()) >= 0:
+        go_b, go_i, go_j = 0, g.stride(0), g.stride(1)          # (a strided matrix - a transpose, a slice - is read in place)
+    else:
+        g = g.expand(bshape + (n1, n2)).contiguous()
+        go_b, go_i, go_j = n1 * n2, n2, 1
+    if wrt == 1:
+        first, second, m1, m2, sf, ss, sgn = a2, b2, n1, n2, s1, s2, 1.0
+    else:
+        first, second, m1, m2, sf, ss, go_i, go_j, sgn = b2, a2, n2, n1, s2, s1, go_j, go_i, -1.0
+    gx = torch.zeros(bshape + (m1, a.shape[-1]), dtype=torch.float64, device=dev)
+    if gx.numel() == 0 or m2 == 0:
+        return _out(gx, out_device)
+    with _on(dev):
+        _lib.check(lib.gabo_flat_matern_backward(first.data_ptr(), second.data_ptr(), g.data_ptr(), gx.data_ptr(), nb, m1, m2, d, sf, ss,
+                                                 go_b, go_i, go_j, lval, nu2, sgn, _stream_ptr(dev)), "gabo_flat_matern_backward")
+    if sf == 0 and nb > 1:
+        gx = gx.reshape(nb, m1, -1).sum(0).expand(bshape + (m1, a.shape[-1]))
+    return _out(gx, out_device)
+
+
+def flat_matern_from_distance(r, lengthscale, nu, order=0):
+    """Element-wise on a distance tensor (any shape): order 0 the Matern kernel k_nu(r; lengthscale), order 1 its derivative in the lengthscale."""
+    lib = _lib.load()
+    nu2, lval = _matern_nu2(nu), _matern_lengthscale(lengthscale)
+    if order not in (0, 1):
+        raise ValueError(f"order must be 0 or 1, got {order!r}")
+    out_device = r.device
+    dev = _device_for(r)
+    c = _prep(r, dev).contiguous()
+    out = torch.empty_like(c)
+    with _on(dev):
+        _lib.check(lib.gabo_flat_matern_from_distance(c.data_ptr(), out.data_ptr(), c.numel(), lval, nu2, int(order), _stream_ptr(dev)),
+                   "gabo_flat_matern_from_distance")
+    return _out(out, out_device)
+
+
+class _FlatMaternKernelFunction(torch.autograd.Function):
+    """flat_matern_pairwise(x1, x2; lengthscale) with HIP forward and backward (first order), differentiable in x1, x2 and the lengthscale."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, lengthscale, nu, same):
+        lval = _matern_lengthscale(lengthscale)
+        out = flat_matern_pairwise(x1, x1 if same else x2, lval, nu)
+        ctx.save_for_backward(x1, x2)
+        ctx.lval, ctx.nu = lval, nu
+        ctx.ls_shape = lengthscale.shape if torch.is_tensor(lengthscale) else None
+        ctx.ls_device = lengthscale.device if torch.is_tensor(lengthscale) else None
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x1, x2 = ctx.saved_tensors
+        g1 = g2 = gl = None
+        if ctx.needs_input_grad[0]:
+            g1 = flat_matern_backward(x1, x2, grad_out, ctx.lval, ctx.nu, wrt=1).to(x1.dtype)
+        if ctx.needs_input_grad[1]:
+            g2 = flat_matern_backward(x1, x2, grad_out, ctx.lval, ctx.nu, wrt=2).to(x2.dtype)
+        if ctx.needs_input_grad[2]:      # sum_ij g_ij dk_ij/dl: the distance launch, then the element-wise one
+            dist = frobenius_pairwise(x1, x2, 1.0, _lib.GABO_OUT_DISTANCE).to(grad_out.device)
+            gl = (grad_out * flat_matern_from_distance(dist, ctx.lval, ctx.nu, order=1)).sum().reshape(ctx.ls_shape).to(ctx.ls_device)
+        return g1, g2, gl, None, None
+
+
+def flat_matern_kernel(x1, x2, lengthscale, nu):
+    """Differentiable entry point used by SpdFrobeniusMaternKernel / SpdLogEuclideanMaternKernel (first order in x1, x2 and the lengthscale)."""
+    _matern_nu2(nu)
+    if torch.is_tensor(lengthscale):
+        if lengthscale.numel() != 1:
+            raise RuntimeError("gabotorch_amd SPD kernels take a single lengthscale (batch_shape == ())")
+        lengthscale = lengthscale.double()
+    else:
+        lengthscale = torch.tensor(float(lengthscale), dtype=torch.float64)
+    return _FlatMaternKernelFunction.apply(x1, x2, lengthscale, float(nu), x2 is x1)
+
+
 def gp_acquisition(kstar, alpha, linv, linv_t, mean, outputscale, kxx, best_f, kind, maximize, out_sign=1.0, need_grad=True):
     """Fused GP posterior + acquisition on the strip kstar (R x n, base kernel values): -> (value R, d value / d kstar R x n or None).
     All tensors fp64 on one HIP device."""
@@ -1431,6 +1566,36 @@ def gp_mll_series(c, y, coeff, dcoeff, series_dim, outputscale, noise, mean):
         stream = _stream_ptr(dev)
         _lib.check(lib.gabo_gp_mll_series(c.data_ptr(), y.data_ptr(), n, ptr, dptr, na, int(series_dim), float(outputscale), float(noise),
                                           float(mean), host.data_ptr(), stream), "gabo_gp_mll_series")
+        torch.cuda.current_stream(dev).synchronize()
+    return host_np[:6].tolist()
+
+
+def gp_mll_matern(r, y, lengthscale, nu, outputscale, noise, mean):
+    """One evaluation of the exact-GP marginal log likelihood with K = outputscale * k_nu(r; lengthscale) + noise * I, the Matern function of
+    flat_matern_from_distance evaluated inside the launch (gabo_gp_mll_matern): -> [ll, dll/dlengthscale, dll/doutputscale, dll/dnoise,
+    dll/dmean, not_positive_definite] as Python floats.  r: the n x n distance matrix (frobenius_pairwise with GABO_OUT_DISTANCE), fp64 on a
+    HIP device, y: n; nu in {0.5, 1.5, 2.5}.  Beyond GABO_GP_MLL_MAX_N points (up to GABO_GP_MLL_LARGE_MAX_N) the same numbers are composed
+    from the element-wise launches, gabo_gp_mll_large and one reduction."""
+    lib = _lib.load()
+    nu2, lval = _matern_nu2(nu), _matern_lengthscale(lengthscale)
+    dev = r.device
+    n = r.shape[-1]
+    if r.dim() != 2 or r.shape[0] != n or y.numel() != n or not r.is_contiguous() or not y.is_contiguous():
+        raise RuntimeError("gp_mll_matern: r must be a contiguous n x n matrix and y a contiguous vector of n targets")
+    if n > _lib.GABO_GP_MLL_MAX_N:
+        out, w = _gp_mll_large(flat_matern_from_distance(r, lval, nu, 0), y, 0.0, outputscale, noise, mean, True, True)
+        d_l = (0.5 * float(outputscale)) * (w * flat_matern_from_distance(r, lval, nu, 1)).sum()
+        out[1] = torch.where(out[5] == 0, d_l, torch.zeros_like(d_l))
+        return out.tolist()
+    ent = _mll_host_out.get(dev.index)             # (the page-locked result buffer of gp_mll: one launch, one stream wait)
+    if ent is None:
+        host = torch.zeros(8, dtype=torch.float64).pin_memory()
+        ent = _mll_host_out[dev.index] = (host, host.numpy())
+    host, host_np = ent
+    with _on(dev):
+        stream = _stream_ptr(dev)
+        _lib.check(lib.gabo_gp_mll_matern(r.data_ptr(), y.data_ptr(), n, lval, nu2, float(outputscale), float(noise), float(mean),
+                                          host.data_ptr(), stream), "gabo_gp_mll_matern")
         torch.cuda.current_stream(dev).synchronize()
     return host_np[:6].tolist()
 

@@ -317,6 +317,35 @@ int gabo_gp_mll_large(const double* e, const double* y, int64_t n, double theta,
                       double* out, double* w, void* workspace, size_t workspace_bytes, gabo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Matern kernels of smoothness nu = nu2 / 2, nu2 in {1, 3, 5}, on the flat SPD metrics (csrc/flat_matern.hip, csrc/gp_mll_matern.hip).
+ * X -> mandel(logm X) and X -> mandel(X) are isometries of the log-Euclidean and Frobenius metrics into R^{d(d+1)/2}, so the Riemannian
+ * Matern kernel of either is the Euclidean one of the distance r of gabo_frobenius_pairwise on those features (the reference's 1e-15 on
+ * every matrix element included) and is positive definite for every lengthscale.  gpytorch's MaternKernel parametrisation, NOT the
+ * exp(-r^2 / l^2) convention of the Gaussian entries:  a = sqrt(nu2) / l, x = a r,
+ *   k = m(x) exp(-x),  m = 1 | 1 + x | 1 + x + x^2 / 3;   dk/dl = x^2 q(x) exp(-x) / l,  q = 1/x | 1 | (1 + x) / 3;
+ *   2 dk/d(r^2) = -a^2 q(x) exp(-x)  (the weight of the x-gradient; no division by r for nu2 = 3, 5).
+ * Every entry returns GABO_ERR_ARG for nu2 outside {1, 3, 5} or a lengthscale that is not positive and finite, before any HIP call.
+ * gabo_flat_matern_pairwise: shapes, strides, return codes and the NaN rule (a NaN feature gives a NaN value) of gabo_frobenius_pairwise.
+ *   x1 == x2 (the same pointer, n1 == n2, equal batch strides): the pairs above the diagonal take the epsilon with the opposite sign, which
+ *   makes out_ij and out_ji the same bits; the diagonal and the lower triangle are as for two separate sets.
+ * gabo_flat_matern_backward: the arguments of gabo_frobenius_backward with (lengthscale, nu2) in the place of (beta, flags); a fixed
+ *   summation order, so two calls return the same bits.
+ * gabo_flat_matern_from_distance: element-wise on `count` distances; order 0: k, order 1: dk/dl (anything else: GABO_ERR_ARG).
+ * gabo_gp_mll_matern: gabo_gp_mll for Ky = outputscale * k(r) + noise * I with r the n x n distance matrix (row-major, the lower triangle
+ *   and the diagonal are read), n <= GABO_GP_MLL_MAX_N (GABO_ERR_DIM beyond).  out[1] = d out[0] / d lengthscale =
+ *   outputscale * sum_ij W_ij dk_ij/dl / 2; out[0], out[2..5] have the bits of gabo_gp_mll_gram on gabo_flat_matern_from_distance(r). */
+int gabo_flat_matern_pairwise(const double* x1, const double* x2, double* out, int64_t batch, int64_t n1, int64_t n2, int d,
+                              int64_t x1_batch_stride, int64_t x2_batch_stride, double lengthscale, int nu2, gabo_stream_t stream);
+int gabo_flat_matern_backward(const double* x1, const double* x2, const double* grad_out, double* grad_x1, int64_t batch, int64_t n1,
+                              int64_t n2, int d, int64_t x1_batch_stride, int64_t x2_batch_stride, int64_t go_batch_stride,
+                              int64_t go_row_stride, int64_t go_col_stride, double lengthscale, int nu2, double eps_sign,
+                              gabo_stream_t stream);
+int gabo_flat_matern_from_distance(const double* r, double* out, int64_t count, double lengthscale, int nu2, int order,
+                                   gabo_stream_t stream);
+int gabo_gp_mll_matern(const double* r, const double* y, int64_t n, double lengthscale, int nu2, double outputscale, double noise,
+                       double mean, double* out, gabo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Extreme eigenvalues of the kernel matrices of a kernel-parameter study, all (point set, parameter) pairs in one launch
  * (examples/kernels/spd/spd_gaussian_kernel_parameters.py:84-125 and examples/kernels/sphere/sphere_gaussian_kernel_parameters.py:62-112:
  * per pair one kernel.forward and one np.linalg.eig on the host, of which the minimum is kept).
