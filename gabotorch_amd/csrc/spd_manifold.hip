@@ -508,6 +508,27 @@ __global__ __launch_bounds__(256) void frobenius_backward_kernel(const double* _
 // Sphere manifold operations, one lane per point (dim is small): x, u, v: n x dim.
 enum { SOP_PROJ = 0, SOP_RETR = 1, SOP_EXP = 2, SOP_LOG = 3, SOP_DIST = 4, SOP_EHESS2RHESS = 5 };
 
+// The angle t between unit vectors x and y from the CHORD, not from acos(<x,y>): |y - x| = 2 sin(t/2), and past a right angle |y + x| = 2 cos(t/2).
+// acos turns the rounding of <x,y> (an ulp of 1) into an error of ulp / sin t in t: 1.5e-8 for two copies of one unit vector whose squared norm
+// rounds below 1, where dist must be 0 and log must take its identity branch.  The chord is a sum of squares of (near the ends: exact) differences,
+// so t comes out to a few ulp of ITSELF at every angle.  far: <x,y> < 0;  chord: y - x (far: y + x) is what the caller forms again;
+// h = |chord|^2 / 2 = 1 - cos t (far: 1 + cos t);  sn = sin t.
+struct SphereAngle { double th, sn, h; bool far; };
+static __device__ __forceinline__ SphereAngle sphere_angle(const double* __restrict__ X, const double* __restrict__ Y, int dim) {
+    double ip = 0.0;
+    for (int k = 0; k < dim; ++k) ip = __builtin_fma(X[k], Y[k], ip);
+    SphereAngle a;
+    a.far = ip < 0.0;
+    double cc = 0.0;
+    for (int k = 0; k < dim; ++k) { const double c = a.far ? Y[k] + X[k] : Y[k] - X[k]; cc = __builtin_fma(c, c, cc); }
+    const double hs = 0.5 * __builtin_sqrt(cc);               // sin(t/2), far: cos(t/2); at most sqrt(1/2) up to rounding
+    const double phi = 2.0 * asin(hs > 1.0 ? 1.0 : hs);
+    a.th = a.far ? 3.14159265358979323846 - phi : phi;
+    a.sn = sin(phi);                                          // sin(pi - phi) = sin(phi)
+    a.h = 0.5 * cc;
+    return a;
+}
+
 __global__ __launch_bounds__(256) void sphere_manifold_kernel(int op, const double* __restrict__ x, const double* __restrict__ u,
                                                               const double* __restrict__ v, const double* __restrict__ w,
                                                               double* __restrict__ out, int64_t n, int dim) {
@@ -542,24 +563,19 @@ __global__ __launch_bounds__(256) void sphere_manifold_kernel(int op, const doub
             }
             break;
         }
-        case SOP_LOG: {  // (y - x cos t) t / sin t, t = acos(clip(<x,y>)); 0 where t < 1e-16   sphere_utils.py:41-65 (base = x, point = u)
-            double ip = 0.0;
-            for (int k = 0; k < dim; ++k) ip = __builtin_fma(X[k], U[k], ip);
-            ip = ip > 1.0 ? 1.0 : (ip < -1.0 ? -1.0 : ip);
-            double th = acos(ip);
-            if (th < 1e-16) {
+        case SOP_LOG: {  // (y - x cos t) t / sin t, t = the angle between x and y; 0 where t < 1e-16   sphere_utils.py:41-65 (base = x, point = u)
+            const SphereAngle a = sphere_angle(X, U, dim);
+            if (a.th < 1e-16 || a.sn == 0.0) {       // (sn = 0 away from t = 0: the antipode, where the chord y + x is 0 as well; a NaN goes on)
                 for (int k = 0; k < dim; ++k) O[k] = 0.0;
             } else {
-                double cn = cos(th), f = th / sin(th);
-                for (int k = 0; k < dim; ++k) O[k] = (U[k] - X[k] * cn) * f;
+                // y - x cos t = (y - x) + x (1 - cos t) = (y + x) - x (1 + cos t): no cancellation against a rounded cosine
+                const double f = a.th / a.sn, xs = a.far ? -a.h : a.h;
+                for (int k = 0; k < dim; ++k) O[k] = ((a.far ? U[k] + X[k] : U[k] - X[k]) + X[k] * xs) * f;
             }
             break;
         }
-        case SOP_DIST: {  // acos(clip(<x,y>, -1, 1))              [3P] Sphere.dist
-            double ip = 0.0;
-            for (int k = 0; k < dim; ++k) ip = __builtin_fma(X[k], U[k], ip);
-            ip = ip > 1.0 ? 1.0 : (ip < -1.0 ? -1.0 : ip);
-            out[i] = acos(ip);
+        case SOP_DIST: {  // the angle between x and y (acos(clip(<x,y>, -1, 1)), sphere_angle)              [3P] Sphere.dist
+            out[i] = sphere_angle(X, U, dim).th;
             break;
         }
         case SOP_EHESS2RHESS: {  // proj(x, eh) - <x, eg> u : u = egrad, v = ehess, w = tangent    [3P]
