@@ -10,7 +10,11 @@ The reconstruction parameters (complement basis, bottom block, contraction) are 
 (optimize_reconstruction_parameters_nested_spd with the log-Euclidean cost, hd_gabo_spd.py:229-232; augmented Lagrangian + conjugate
 gradients, --rec-iters 0 skips it and uses the orthogonal complement of W, C = I, K = 0).
 
-    python examples/hd_gabo_spd.py [--dim 5] [--latent 2] [--iters 10]
+    python examples/hd_gabo_spd.py [--dim 5] [--latent 2] [--iters 10] [--kernel gaussian|matern52]
+
+--kernel matern52: the surrogate is the nu = 5/2 Matern kernel of the log-Euclidean metric after the nested projection
+(NestedSpdLogEuclideanMaternKernel, fitted with one host call per evaluation) and the latent GP takes SpdLogEuclideanMaternKernel with the
+fitted lengthscale; the acquisition then runs the separate-launch chain, as in examples/gabo_spd.py --kernel matern52.
 """
 import argparse
 import functools
@@ -25,7 +29,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gabotorch_amd import manifolds, models, ops                                                                 # noqa: E402
 from gabotorch_amd._compat import ScaleKernel                                                                     # noqa: E402
 from gabotorch_amd.BO_test_functions.test_functions import rosenbrock_function_spd                                # noqa: E402
-from gabotorch_amd.kernel_utils.kernels_spd import NestedSpdLogEuclideanGaussianKernel, SpdLogEuclideanGaussianKernel    # noqa: E402
+from gabotorch_amd.kernel_utils.kernels_spd import (NestedSpdLogEuclideanGaussianKernel, NestedSpdLogEuclideanMaternKernel,   # noqa: E402
+                                                    SpdLogEuclideanGaussianKernel, SpdLogEuclideanMaternKernel)
 from gabotorch_amd.manifold_optimization.conjugate_gradient import ConjugateGradient                              # noqa: E402
 from gabotorch_amd.manifold_optimization.manifold_gp_fit import fit_gpytorch_manifold                             # noqa: E402
 from gabotorch_amd.manifold_optimization.batched_trust_regions import BatchedTrustRegions                         # noqa: E402
@@ -42,9 +47,11 @@ from gabotorch_amd.Riemannian_utils.spd_utils_torch import (symmetric_matrix_to_
 
 
 def run(dim=5, latent=2, iters=10, restarts=5, raw=100, seed=1234, device="cuda:0", verbose=True, fit_iters=50, rec_iters=6,
-        timings=None):
+        timings=None, kernel="gaussian"):
     """timings: optional dict; the wall-clock seconds of the phases of every iteration are appended to its lists."""
     import time
+    if kernel not in ("gaussian", "matern52"):
+        raise ValueError(f"kernel must be 'gaussian' or 'matern52', got {kernel!r}")
 
     def lap(name, since):
         if timings is not None:
@@ -65,7 +72,8 @@ def run(dim=5, latent=2, iters=10, restarts=5, raw=100, seed=1234, device="cuda:
     x_data = torch.tensor(np.stack([symmetric_matrix_to_vector_mandel(big.rand()) for _ in range(5)]), device=device)
     y_data = torch.cat([objective(x) for x in x_data]).reshape(-1).to(device)
     solver = BatchedTrustRegions(mingradnorm=2e-4, maxiter=100, minstepsize=1e-4, strict_constraints=True)   # hd_gabo_spd.py:194
-    k_fct = ScaleKernel(NestedSpdLogEuclideanGaussianKernel(dim, latent), outputscale_prior=models.GammaPrior(2.0, 0.15)).double()
+    nested = NestedSpdLogEuclideanGaussianKernel(dim, latent) if kernel == "gaussian" else NestedSpdLogEuclideanMaternKernel(dim, latent, nu=2.5)
+    k_fct = ScaleKernel(nested, outputscale_prior=models.GammaPrior(2.0, 0.15)).double()
     ops.set_error_checking(False)
     best = [float(y_data.min())]
     for it in range(iters):
@@ -84,7 +92,7 @@ def run(dim=5, latent=2, iters=10, restarts=5, raw=100, seed=1234, device="cuda:
         else:
             V = torch.linalg.svd(W, full_matrices=True)[0][:, latent:]              # orthonormal complement of span(W)
         tick = lap("reconstruction", tick)
-        latent_kernel = SpdLogEuclideanGaussianKernel().double()
+        latent_kernel = (SpdLogEuclideanGaussianKernel() if kernel == "gaussian" else SpdLogEuclideanMaternKernel(nu=2.5)).double()
         latent_kernel.lengthscale = k_fct.base_kernel.lengthscale.detach().clone()   # same hyper-parameters (:217-219)
         # constraints and raw samples of the latent optimisation are stated in the ORIGINAL space (:239-256)
         small.rand = types.MethodType(functools.partial(random_nested_spd_with_spd_eigenvalue_constraints, random_spd_fct=big.rand,
@@ -120,5 +128,6 @@ if __name__ == "__main__":
     ap.add_argument("--latent", type=int, default=2)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rec-iters", type=int, default=6)
+    ap.add_argument("--kernel", choices=["gaussian", "matern52"], default="gaussian")
     a = ap.parse_args()
-    run(a.dim, a.latent, a.iters, rec_iters=a.rec_iters)
+    run(a.dim, a.latent, a.iters, rec_iters=a.rec_iters, kernel=a.kernel)

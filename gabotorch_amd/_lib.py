@@ -109,6 +109,7 @@ SIGNATURES = {
     "gabo_spd_ai_backward2": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _I64, _I64, _I64, _I64, _I64, _D, _I, _P, _SZ, _P, _P]),
     "gabo_nested_spd_gram_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
     "gabo_nested_spd_gram": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _I, _I, _D, _I, _P, _SZ, _P, _P]),
+    "gabo_nested_spd_matern_gram": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _I, _D, _I, _P, _SZ, _P, _P]),
     "gabo_sphere_pairwise": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, _I64, _I64, _D, _I, _I, _P]),
     "gabo_sphere_ktable_doubles": (_I64, []),
     "gabo_sphere_pairwise_uses_ktable": (_I, [_I64, _I64, _I64, _I, _D, _I, _I]),
@@ -220,6 +221,7 @@ SIGNATURES = {
     "gabo_nested_sphere_fit_evaluate_series": (_I, [_P, _P, _P, _P, _I64, _I, _I, _P, _P, _I, _D, _D, _D, _I, _P, _P, _SZ, _P, _SZ, _P]),
     "gabo_nested_spd_fit_workspace_bytes": (_SZ, [_I64, _I, _I]),
     "gabo_nested_spd_fit_evaluate": (_I, [_P, _P, _P, _P, _I64, _I, _I, _D, _D, _D, _D, _I, _P, _P, _SZ, _P, _SZ, _P]),
+    "gabo_nested_spd_fit_evaluate_matern": (_I, [_P, _P, _P, _P, _I64, _I, _I, _D, _I, _D, _D, _D, _I, _P, _P, _SZ, _P, _SZ, _P]),
     "gabo_nested_spd_reconstruction_solve_workspace_bytes": (None, [_I64, _I, _I, _P, _P]),
     "gabo_nested_spd_reconstruction_solve": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I, _I, _I, _P, _SZ, _P, _SZ, _P, _P, _P]),
     "gabo_nested_spd_reconstruction_solve_with": (_I, [ReconEvalFn, _P, _P, _P, _P, _P, _P, _I, _I, _P, _SZ, _P, _P]),

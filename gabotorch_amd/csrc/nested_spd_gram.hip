@@ -8,6 +8,7 @@
 // finishes each d x d result in the lanes' registers - Cholesky factor (+ inverse for x1) in the layouts of spd_prep.hpp, or the Mandel vector of
 // its matrix logarithm - straight into the workspace of the Gram launch (spd_ai_gauss2_kernel / spd_ai_pairwise_kernel, frobenius_pairwise_kernel).
 // No gradient (the differentiable route stays gabo_spd_project / gabo_spd_logm_mandel / the pairwise kernels and their backward launches).
+#include "flat_matern.hpp"
 #include "gabo_device.hpp"
 #include "spd_eigvec.hpp"
 #include "spd_prep.hpp"
@@ -138,4 +139,33 @@ extern "C" int gabo_nested_spd_gram(const double* x1, const double* x2, const do
         return gabo_frobenius_pairwise(o1, f2, out, batch, n1, n2, dl, n1 * T, n2 * T, beta, flags & GABO_OUT_MASK, stream);
     }
     return gabo::launch_spd_ai_prepared(dl, out, batch, n1, n2, false, false, beta, flags, o1, st);
+}
+
+// The same two launches with the Matern Gram of the log-Euclidean features (NestedSpdLogEuclideanMaternKernel.forward when no gradient is
+// requested): nested_spd_prepare_kernel<DL, true>, then gabo_flat_matern_pairwise on its output - with x1 == x2 on one buffer, hence a matrix
+// that is symmetric to the last bit.
+extern "C" int gabo_nested_spd_matern_gram(const double* x1, const double* x2, const double* w, double* out, int64_t batch, int64_t n1, int64_t n2,
+                                           int D, int dl, double lengthscale, int nu2, void* workspace, size_t workspace_bytes, int* status,
+                                           gabo_stream_t stream) {
+    if (!gabo::flat_matern_arguments_ok(lengthscale, nu2)) return GABO_ERR_ARG;
+    if (batch < 0 || n1 < 0 || n2 < 0) return GABO_ERR_ARG;
+    if (D < 2 || D > GABO_SPD_MAX_DIM || dl < 2 || dl > 4 || dl > D) return GABO_ERR_DIM;
+    if (batch == 0 || n1 == 0 || n2 == 0) return GABO_OK;
+    if (!x1 || !x2 || !w || !out || !workspace || !status) return GABO_ERR_ARG;
+    if (workspace_bytes < gabo_nested_spd_gram_workspace_bytes(batch, n1, n2, dl)) return GABO_ERR_ARG;
+    const size_t lds = (size_t)(D * dl + (dl * (dl + 1) / 2) * (D * (D + 1) / 2)) * sizeof(double);
+    if (lds > 48 * 1024) return GABO_ERR_DIM;
+    hipStream_t st = (hipStream_t)stream;
+    const int T = dl * (dl + 1) / 2;
+    const int same = (x1 == x2 && n1 == n2) ? 1 : 0;
+    const int64_t m1 = batch * n1, m2 = same ? 0 : batch * n2;
+    double* o1 = (double*)workspace;
+    double* o2 = o1 + m1 * T;
+    switch (dl) {
+        case 2: gabo::launch_nested_prepare<2, true>(x1, x2, w, o1, o2, m1, m2, n2, D, same, status, st); break;
+        case 3: gabo::launch_nested_prepare<3, true>(x1, x2, w, o1, o2, m1, m2, n2, D, same, status, st); break;
+        default: gabo::launch_nested_prepare<4, true>(x1, x2, w, o1, o2, m1, m2, n2, D, same, status, st); break;
+    }
+    if (hipGetLastError() != hipSuccess) return GABO_ERR_LAUNCH;
+    return gabo_flat_matern_pairwise(o1, same ? o1 : o2, out, batch, n1, n2, dl, n1 * T, n2 * T, lengthscale, nu2, stream);
 }

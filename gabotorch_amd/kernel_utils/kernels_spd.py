@@ -157,13 +157,12 @@ def _beta_from_lengthscale(ls):
     return 1.0 / (ls * ls)
 
 
-class NestedSpdAffineInvariantGaussianKernel(_BetaKernel):
-    """Affine-invariant Gaussian kernel after the nested projection Y = W^T X W, W in G(D, d)
-    (kernel_utils/kernels_nested_spd.py:19-136).  The projection matrix is a plain parameter here (pymanopt's Grassmann
-    manifold, used by the reference only to draw the initial W, is replaced by qr(randn))."""
+class _NestedProjection:
+    """The projection matrix W in G(D, d) of the nested SPD kernels: a plain parameter, drawn as qr(randn) after the base kernel's own
+    parameters (one torch.randn call, so the nested classes start from the same W under one seed), with its manifold for
+    fit_gpytorch_manifold."""
 
-    def __init__(self, dim, latent_dim, beta_min, beta_prior=None, **kwargs):
-        super().__init__(beta_min, beta_prior, **kwargs)
+    def _init_projection(self, dim, latent_dim):
         self.dim, self.latent_dim = dim, latent_dim
         q, _ = torch.linalg.qr(torch.randn(dim, latent_dim, dtype=torch.float64))
         self.register_parameter(name="raw_projection_matrix", parameter=torch.nn.Parameter(q.repeat(*self.batch_shape, 1, 1)))
@@ -177,6 +176,16 @@ class NestedSpdAffineInvariantGaussianKernel(_BetaKernel):
     @projection_matrix.setter
     def projection_matrix(self, value):
         self.initialize(raw_projection_matrix=value)
+
+
+class NestedSpdAffineInvariantGaussianKernel(_NestedProjection, _BetaKernel):
+    """Affine-invariant Gaussian kernel after the nested projection Y = W^T X W, W in G(D, d)
+    (kernel_utils/kernels_nested_spd.py:19-136).  The projection matrix is a plain parameter here (pymanopt's Grassmann
+    manifold, used by the reference only to draw the initial W, is replaced by qr(randn))."""
+
+    def __init__(self, dim, latent_dim, beta_min, beta_prior=None, **kwargs):
+        super().__init__(beta_min, beta_prior, **kwargs)
+        self._init_projection(dim, latent_dim)
 
     def forward(self, x1, x2, diagonal_distance=False, **params):
         if diagonal_distance is True:
@@ -190,24 +199,12 @@ class NestedSpdAffineInvariantGaussianKernel(_BetaKernel):
         return ops.spd_ai_kernel(p1, p2, beta, _lib.GABO_OUT_GAUSSIAN)
 
 
-class NestedSpdLogEuclideanGaussianKernel(SpdLogEuclideanGaussianKernel):
+class NestedSpdLogEuclideanGaussianKernel(_NestedProjection, SpdLogEuclideanGaussianKernel):
     """Log-Euclidean Gaussian kernel after the nested projection   (kernels_nested_spd.py:139-246; the kernel examples/hd_gabo_spd.py:164 uses)."""
 
     def __init__(self, dim, latent_dim, **kwargs):
         super().__init__(**kwargs)
-        self.dim, self.latent_dim = dim, latent_dim
-        q, _ = torch.linalg.qr(torch.randn(dim, latent_dim, dtype=torch.float64))
-        self.register_parameter(name="raw_projection_matrix", parameter=torch.nn.Parameter(q.repeat(*self.batch_shape, 1, 1)))
-        from ..manifold_optimization.host_manifolds import Grassmann
-        self.raw_projection_matrix_manifold = Grassmann(dim, latent_dim)          # kernels_nested_spd.py:75,175
-
-    @property
-    def projection_matrix(self):
-        return self.raw_projection_matrix
-
-    @projection_matrix.setter
-    def projection_matrix(self, value):
-        self.initialize(raw_projection_matrix=value)
+        self._init_projection(dim, latent_dim)
 
     def forward(self, x1, x2, diagonal_distance=False, **params):
         if diagonal_distance is True:
@@ -215,6 +212,26 @@ class NestedSpdLogEuclideanGaussianKernel(SpdLogEuclideanGaussianKernel):
         w = self.projection_matrix.double()
         if ops.nested_spd_gram_applicable(x1, x2, w, self.lengthscale):      # projection + logm in one launch, then the Frobenius Gram
             return ops.nested_spd_gram(x1, x2, w, float(_beta_from_lengthscale(self.lengthscale)), _lib.GABO_METRIC_LOG_EUCLIDEAN)
+        p1 = ops.spd_project_diff(x1, w)
+        p2 = p1 if x2 is x1 else ops.spd_project_diff(x2, w)
+        return super().forward(p1, p2)
+
+
+class NestedSpdLogEuclideanMaternKernel(_NestedProjection, SpdLogEuclideanMaternKernel):
+    """Log-Euclidean Matern kernel (nu = 0.5, 1.5, 2.5, fixed) after the nested projection Y = W^T X W, W in G(D, d): positive definite for
+    every lengthscale and every W, one `lengthscale` in gpytorch's Matern parametrisation.  The projection matrix, its property and its manifold
+    are those of NestedSpdLogEuclideanGaussianKernel; under one torch.manual_seed both classes start from the same W."""
+
+    def __init__(self, dim, latent_dim, nu=2.5, **kwargs):
+        super().__init__(nu=nu, **kwargs)
+        self._init_projection(dim, latent_dim)
+
+    def forward(self, x1, x2, diagonal_distance=False, **params):
+        if diagonal_distance is True:
+            return _diag_ones(x2)
+        w = self.projection_matrix.double()
+        if ops.nested_spd_gram_applicable(x1, x2, w, self.lengthscale):      # projection + logm in one launch, then the Matern Gram
+            return ops.nested_spd_matern_gram(x1, x2, w, self.lengthscale.double().reshape(()), self.nu)
         p1 = ops.spd_project_diff(x1, w)
         p2 = p1 if x2 is x1 else ops.spd_project_diff(x2, w)
         return super().forward(p1, p2)

@@ -120,7 +120,9 @@ class _NestedSpdMllProblem(_OneCallMllProblem):
     d ll / d Gram up to outputscale / 2), the projection's adjoint dW = 2 sum_n X_n W G_n, and one read-back.  The log-Euclidean kernel's chain
     is one host call (gabo_nested_spd_fit_evaluate: the same launches issued from C++); `native = False` and the affine-invariant kernel issue
     it launch by launch (`_evaluate`).  Round 2 differentiated the same launches through torch autograd: 0.3 ms per value, 1.0 ms per gradient
-    at n = 10."""
+    at n = 10.
+    ScaleKernel(NestedSpdLogEuclideanMaternKernel) takes gabo_nested_spd_fit_evaluate_matern (`matern` = nu): the scalar handed to the call is the
+    lengthscale itself and a lengthscale prior is on it; `native = False` issues that chain launch by launch too (`_evaluate_matern`)."""
 
     @staticmethod
     def build(model, names, params, manifold):
@@ -128,7 +130,8 @@ class _NestedSpdMllProblem(_OneCallMllProblem):
         from ..kernel_utils import kernels_spd as kspd
         cm = model.covar_module
         base = getattr(cm, "base_kernel", None)
-        if _compat.HAVE_GPYTORCH or base is None or type(base) not in (kspd.NestedSpdLogEuclideanGaussianKernel, kspd.NestedSpdAffineInvariantGaussianKernel):
+        if _compat.HAVE_GPYTORCH or base is None or type(base) not in (kspd.NestedSpdLogEuclideanGaussianKernel, kspd.NestedSpdAffineInvariantGaussianKernel,
+                                                                            kspd.NestedSpdLogEuclideanMaternKernel):
             return None
         iw = [k for k, p in enumerate(params) if p is base.raw_projection_matrix]
         if len(iw) != 1 or base.raw_projection_matrix.dim() != 2 or not model.train_x.is_cuda and not torch.cuda.is_available():
@@ -143,26 +146,35 @@ class _NestedSpdMllProblem(_OneCallMllProblem):
         if any(params[k].numel() != 1 for k in self.scalar_idx):
             return None
         self.log_euclidean = type(base) is kspd.NestedSpdLogEuclideanGaussianKernel
+        self.matern = float(base.nu) if type(base) is kspd.NestedSpdLogEuclideanMaternKernel else None
         self._setup(model, ops)
         self.xm = ops.mandel_to_matrix(self.x)                          # n x D x D, fixed during the fit (projection adjoint)
         self.W, self.native = None, True
-        self.scalar = model._fast_scalar_objective([params[k] for k in self.scalar_idx], evaluator=self._evaluate)
+        self.scalar = model._fast_scalar_objective([params[k] for k in self.scalar_idx], evaluator=self._evaluate,
+                                                   evaluator_takes_value=self.matern is not None)
         return self if self.scalar is not None else None
+
+    def _in_one_call(self):
+        return (self.log_euclidean or self.matern is not None) and self.native
 
     def _sizes(self, lib):
         D, d = self.point.shape
         return lib.gabo_nested_spd_fit_workspace_bytes(self.x.shape[0], D, d), 2 * D * d + 7, D * d
 
     def _call(self, lib, ptr, theta, outputscale, noise, mean, want, *buffers):
-        return lib.gabo_nested_spd_fit_evaluate(self.x.data_ptr(), self.xm.data_ptr(), self.y.data_ptr(), ptr(self.point), self.x.shape[0],
-                                                self.point.shape[0], self.point.shape[1], theta, outputscale, noise, mean, want,
-                                                *buffers), "gabo_nested_spd_fit_evaluate"
+        head = (self.x.data_ptr(), self.xm.data_ptr(), self.y.data_ptr(), ptr(self.point), self.x.shape[0], self.point.shape[0], self.point.shape[1])
+        if self.matern is not None:            # theta is the lengthscale (evaluator_takes_value)
+            return (lib.gabo_nested_spd_fit_evaluate_matern(*head, theta, int(round(2.0 * self.matern)), outputscale, noise, mean, want, *buffers),
+                    "gabo_nested_spd_fit_evaluate_matern")
+        return lib.gabo_nested_spd_fit_evaluate(*head, theta, outputscale, noise, mean, want, *buffers), "gabo_nested_spd_fit_evaluate"
 
     def _evaluate(self, theta, outputscale, noise, mean):
         from .. import _lib
         ops = self.ops
-        if self.log_euclidean and self.native:
+        if self._in_one_call():
             return self._one_call(theta, outputscale, noise, mean)
+        if self.matern is not None:
+            return self._evaluate_matern(theta, outputscale, noise, mean)
         z = ops.spd_project(self.x, self.W)
         if self.log_euclidean:
             feat = ops.spd_logm_mandel(z)
@@ -187,8 +199,30 @@ class _NestedSpdMllProblem(_OneCallMllProblem):
         self.tail = np.asarray(flat[7:])
         return flat[0], flat[6], flat[2], flat[3], flat[4], flat[5]
 
+    def _evaluate_matern(self, lengthscale, outputscale, noise, mean):
+        """gabo_nested_spd_fit_evaluate_matern's chain launch by launch: the feature gradient as autograd forms it (wrt = 1 and wrt = 2: the
+        epsilon enters with opposite signs, so the diagonal pair cancels), d / d lengthscale by the distance launch and the element-wise one."""
+        from .. import _lib
+        ops, nu = self.ops, self.matern
+        z = ops.spd_project(self.x, self.W)
+        feat = ops.spd_logm_mandel(z)
+        kb = ops.flat_matern_pairwise(feat, feat, lengthscale, nu)
+        out, wm = ops.gp_mll_gram(kb, self.y, outputscale, noise, mean, want_w=self.want_grad)
+        if not self.want_grad:
+            o = out.tolist()
+            return o[0], 0.0, o[2], o[3], o[4], o[5]
+        gkb = (0.5 * outputscale) * wm                                   # d ll / d kb
+        gfeat = ops.flat_matern_backward(feat, feat, gkb, lengthscale, nu, wrt=1) + ops.flat_matern_backward(feat, feat, gkb, lengthscale, nu, wrt=2)
+        dist = ops.frobenius_pairwise(feat, feat, 1.0, _lib.GABO_OUT_DISTANCE)
+        g_ls = (gkb * ops.flat_matern_from_distance(dist, lengthscale, nu, order=1)).sum()
+        gm = ops.mandel_to_matrix(ops.spd_logm_mandel_backward(z, gfeat))          # n x d x d (symmetric)
+        gw = 2.0 * torch.einsum("nab,bc,ncd->ad", self.xm, self.W, gm)
+        flat = torch.cat([out, g_ls.reshape(1), gw.reshape(-1)]).tolist()          # one read-back
+        self.tail = np.asarray(flat[7:])
+        return flat[0], flat[6], flat[2], flat[3], flat[4], flat[5]
+
     def _set_point(self, x):
-        if self.log_euclidean and self.native:
+        if self._in_one_call():
             self.point = np.ascontiguousarray(np.asarray(x[self.iw], dtype=np.float64).reshape(self.params[self.iw].shape))
         else:
             self.W = torch.as_tensor(np.asarray(x[self.iw], dtype=np.float64), device=self.x.device).reshape(self.params[self.iw].shape).contiguous()

@@ -1085,6 +1085,42 @@ def nested_spd_gram(x1, x2, w, beta, metric=_lib.GABO_METRIC_AFFINE_INVARIANT, m
     return _out(out, out_device)
 
 
+def nested_spd_matern_gram(x1, x2, w, lengthscale, nu):
+    """Gram matrix of NestedSpdLogEuclideanMaternKernel in two launches, no gradient (gabo_nested_spd_matern_gram): shapes as nested_spd_gram;
+    out = k_nu(||logm Y1 - logm Y2 + 1e-15||_F; lengthscale) of the projected points, nu in {0.5, 1.5, 2.5}, gpytorch's MaternKernel
+    parametrisation.  With `x2 is x1` the set is projected once and the matrix is symmetric to the last bit."""
+    lib = _lib.load()
+    nu2, lval = _matern_nu2(nu), _matern_lengthscale(lengthscale)
+    if x1.shape[:-2] != x2.shape[:-2] or x1.shape[-1] != x2.shape[-1]:
+        raise RuntimeError(f"batch/feature shapes differ: {tuple(x1.shape)} vs {tuple(x2.shape)} (no broadcasting, as in the reference)")
+    out_device = x1.device
+    dev = _device_for(x1, x2, w)
+    same = x2 is x1
+    a = _prep(x1, dev).contiguous()
+    b = a if same else _prep(x2, dev).contiguous()
+    W = _prep(w, dev).contiguous()
+    D = _mandel_dim(a.shape[-1])
+    if W.dim() != 2 or W.shape[0] != D:
+        raise RuntimeError(f"projection matrix must be ({D}, d_latent), got {tuple(W.shape)}")
+    dl = int(W.shape[1])
+    n1, n2 = a.shape[-2], b.shape[-2]
+    bshape = a.shape[:-2]
+    nb = 1
+    for k in bshape:
+        nb *= int(k)
+    out = torch.empty(bshape + (n1, n2), dtype=torch.float64, device=dev)
+    if out.numel() == 0:
+        return _out(out, out_device)
+    wsb = lib.gabo_nested_spd_gram_workspace_bytes(nb, n1, n2, dl)
+    ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
+    status = _status_word(dev)
+    with _on(dev):
+        rc = lib.gabo_nested_spd_matern_gram(a.data_ptr(), b.data_ptr(), W.data_ptr(), out.data_ptr(), nb, n1, n2, D, dl, lval, nu2, ws.data_ptr(), wsb,
+                                             status.data_ptr(), _stream_ptr(dev))
+    _check_launch(rc, status, "gabo_nested_spd_matern_gram")
+    return _out(out, out_device)
+
+
 def nested_spd_gram_applicable(x1, x2, w, *params):
     """the fused two-launch Gram serves evaluations that nobody differentiates, latent dimensions 2 ... 4 and dense, equally batched inputs"""
     if torch.is_grad_enabled() and any(torch.is_tensor(t_) and t_.requires_grad for t_ in (x1, x2, w) + params):

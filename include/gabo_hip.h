@@ -221,6 +221,14 @@ int gabo_frobenius_pairwise(const double* x1, const double* x2, double* out, int
 size_t gabo_nested_spd_gram_workspace_bytes(int64_t batch, int64_t n1, int64_t n2, int dl);
 int gabo_nested_spd_gram(const double* x1, const double* x2, const double* w, double* out, int64_t batch, int64_t n1, int64_t n2, int D, int dl,
                          int metric, double beta, int flags, void* workspace, size_t workspace_bytes, int* status, gabo_stream_t stream);
+/* gabo_nested_spd_matern_gram: the same two launches for NestedSpdLogEuclideanMaternKernel.forward when no gradient is requested - projection +
+ * logm of both point sets in one launch, then gabo_flat_matern_pairwise on the log-Euclidean features: out = k_nu(||logm Y1 - logm Y2 + 1e-15||_F;
+ * lengthscale), nu2 = 2 nu in {1, 3, 5}, gpytorch's MaternKernel parametrisation.  Shapes, limits, workspace (gabo_nested_spd_gram_workspace_bytes),
+ * status and return codes of gabo_nested_spd_gram with GABO_METRIC_LOG_EUCLIDEAN; before them GABO_ERR_ARG for nu2 outside {1, 3, 5} or a
+ * lengthscale that is not positive and finite - before any HIP call.  x1 == x2 (same pointer, n1 == n2): the set is projected once and the
+ * matrix is symmetric to the last bit. */
+int gabo_nested_spd_matern_gram(const double* x1, const double* x2, const double* w, double* out, int64_t batch, int64_t n1, int64_t n2, int D,
+                                int dl, double lengthscale, int nu2, void* workspace, size_t workspace_bytes, int* status, gabo_stream_t stream);
 
 /* Gradients of the two calls above (the reference differentiates them by autograd; kernels_spd.py:238-240,305-311).
  * gabo_spd_logm_mandel_backward: grad_x = Mandel( V ((V^T G V) o F) V^T ), the adjoint Frechet derivative of logm at X applied
@@ -451,6 +459,21 @@ size_t gabo_nested_spd_fit_workspace_bytes(int64_t n, int D, int d);
 int gabo_nested_spd_fit_evaluate(const double* x_mandel, const double* x_matrices, const double* y, const double* w_host, int64_t n, int D,
                                  int d, double theta, double outputscale, double noise, double mean, int want_grad, double* out_host,
                                  void* workspace, size_t workspace_bytes, double* pinned, size_t pinned_doubles, gabo_stream_t stream);
+/* gabo_nested_spd_fit_evaluate_matern: the same call for ScaleKernel(NestedSpdLogEuclideanMaternKernel): the kernel of the latent points is the
+ * Matern kernel k_nu(r; lengthscale) of r = ||logm Y_i - logm Y_j + 1e-15||_F (gabo_flat_matern_pairwise; nu2 = 2 nu in {1, 3, 5}, gpytorch's
+ * parametrisation).  Arguments, limits and out_host as above with out[6] = d ll / d lengthscale (the lengthscale itself, not theta).
+ * It issues gabo_spd_project, gabo_spd_logm_mandel, gabo_flat_matern_pairwise, the likelihood, ONE launch for the adjoint of the Gram matrix
+ * with respect to the latent features together with d ll / d lengthscale (nested_spd_matern_adjoint_kernel, csrc/nested_spd_fit.hip: the pair
+ * j = i contributes to the lengthscale sum and not to the features; sums in a fixed order, two calls return the same bits),
+ * gabo_spd_logm_mandel_backward and the projection's adjoint.  Coincident distinct training points with nu = 1/2 sit on the kernel's kink: the
+ * gradient there is outside the contract.
+ * workspace: device, gabo_nested_spd_fit_workspace_bytes(n, D, d); pinned: >= 2 D d + 7 doubles of page-locked host memory.
+ * GABO_ERR_DIM for n, D, d outside the limits above; GABO_ERR_ARG for a null pointer, nu2 outside {1, 3, 5}, a lengthscale that is not positive
+ * and finite, a short workspace or pinned buffer - all before any HIP call. */
+int gabo_nested_spd_fit_evaluate_matern(const double* x_mandel, const double* x_matrices, const double* y, const double* w_host, int64_t n, int D,
+                                        int d, double lengthscale, int nu2, double outputscale, double noise, double mean, int want_grad,
+                                        double* out_host, void* workspace, size_t workspace_bytes, double* pinned, size_t pinned_doubles,
+                                        gabo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Nested-sphere mappings over all their levels in one launch (HD-GaBO on the sphere, examples/hd_bo_sphere/benchmark_examples/hd_gabo_sphere.py).
