@@ -133,6 +133,8 @@ SIGNATURES = {
     "gabo_flat_matern_backward": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _I64, _I64, _I64, _I64, _I64, _D, _I, _D, _P]),
     "gabo_flat_matern_from_distance": (_I, [_P, _P, _I64, _D, _I, _I, _P]),
     "gabo_gp_mll_matern": (_I, [_P, _P, _I64, _D, _I, _D, _D, _D, _P, _P]),
+    "gabo_spd_ai_logdiag": (_I, [_P, _P, _P, _I64, _I64, _I, _P]),
+    "gabo_spd_ai_spectral_features": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I, _P]),
     "gabo_gram_extreme_eig_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "gabo_gram_extreme_eig": (_I, [_P, _I64, _I64, _P, _I64, _P, _P, _SZ, _P]),
     "gabo_gp_posterior_joint_workspace_bytes": (_SZ, [_I64, _I64]),

@@ -151,6 +151,72 @@ class SpdLogEuclideanMaternKernel(_FlatMaternKernel):
         return ops.spd_logm_mandel_diff(x)
 
 
+class SpdAffineInvariantMaternKernel(Kernel):
+    """Riemannian Matern (nu > 0) or heat (nu = math.inf) kernel of the affine-invariant metric on S^dim_++, which has no closed form, by the
+    random phase features of non-compact symmetric spaces (Azangulov et al. 2023): k(X, Y) = <F(X), F(Y)> with 2 num_features features per
+    point, each from one order-dim Cholesky factorisation (ops.spd_ai_spectral_features).  A Monte-Carlo approximation of the kernel, error
+    O(1 / sqrt(num_features)), that is positive semi-definite with k(X, X) = 1 for EVERY lengthscale and every seed: one `lengthscale`
+    (exp(-r^2 / (2 lengthscale^2)) is the flat-space limit of the heat kernel, the convention of the sphere and flat-SPD Matern classes), no
+    beta_min.  nu is fixed, not a parameter; the random draw (seed) is fixed at construction and shared by every lengthscale.
+    forward takes the cheapest route that supports the gradients asked for: none - one fused launch per point set; the lengthscale only - the
+    log-diagonals from one launch, remembered for the last point set (a fit computes them once), then element-wise torch; x - a plain torch
+    composition (first order, slow).  dim <= 10 on the device."""
+
+    def __init__(self, dim, nu=2.5, num_features=1024, seed=0, **kwargs):
+        base = ops.spd_ai_spectral_base(dim, num_features, nu, seed)          # (validates dim, num_features and nu)
+        self.has_lengthscale = True
+        super().__init__(has_lengthscale=True, ard_num_dims=None, **kwargs)
+        self.dim, self.nu, self.num_features, self.seed = dim, float(nu), num_features, seed
+        self.spectral_base = base
+        self._phases = {}               # device -> H (L, d, d)
+        self._logdiag_held = None
+
+    def _phases_on(self, device):
+        h = self._phases.get(device)
+        if h is None:
+            h = self._phases[device] = torch.as_tensor(self.spectral_base[2], dtype=torch.float64).to(device)
+        return h
+
+    def _logdiag(self, x, phases):
+        key = (x.data_ptr(), x._version, tuple(x.shape), x.device, x.dtype)
+        held = self._logdiag_held
+        if held is None or held[0] != key:
+            held = self._logdiag_held = (key, ops.spd_ai_logdiag(x, phases), x)      # (holding x keeps its address its own)
+        return held[1]
+
+    def _points(self, x):
+        """(..., N, dv) -> the (M, dv) points to compute features of, and how to shape (M, 2L) back; an expanded batch is one point set"""
+        bshape = x.shape[:-2]
+        if len(bshape) == 0:
+            return x, lambda f: f
+        if all(st == 0 for st, sz in zip(x.stride()[:len(bshape)], bshape) if sz > 1):
+            return x[(0,) * len(bshape)], lambda f: f.expand(bshape + f.shape)
+        return x.reshape(-1, x.shape[-1]), lambda f: f.reshape(bshape + (x.shape[-2], f.shape[-1]))
+
+    def forward(self, x1, x2, diagonal_distance=False, **params):
+        if diagonal_distance is True:
+            return _diag_ones(x2)
+        if x1.shape[-1] != self.dim * (self.dim + 1) // 2 or x2.shape[-1] != x1.shape[-1]:
+            raise RuntimeError(f"expected Mandel vectors of length {self.dim * (self.dim + 1) // 2}, got {tuple(x1.shape)} and {tuple(x2.shape)}")
+        ls = self.lengthscale.double().reshape(())
+        dev = ops._device_for(x1, x2)
+        lam, w = ops.spd_ai_spectral_points(self.spectral_base, ls.to(dev), self.nu)
+        phases = self._phases_on(dev)
+        grad = torch.is_grad_enabled()
+
+        def logdiag_of(x):      # the remembered log-diagonals when only the lengthscale is differentiated
+            return self._logdiag(x, phases) if grad and ls.requires_grad and not x.requires_grad else None
+
+        same = x2 is x1
+        p1, shape1 = self._points(x1)
+        p2, shape2 = (p1, shape1) if same else self._points(x2)
+        if x1.dim() == 2 and x2.dim() == 2:
+            return ops.spd_ai_matern_kernel(p1, p2, phases, lam, w, logdiag1=logdiag_of(p1), logdiag2=None if same else logdiag_of(p2))
+        f1 = shape1(ops.spd_ai_spectral_features(p1, phases, lam, w, logdiag=logdiag_of(p1)))
+        f2 = f1 if same else shape2(ops.spd_ai_spectral_features(p2, phases, lam, w, logdiag=logdiag_of(p2))).to(f1.device)
+        return f1 @ f2.transpose(-1, -2)
+
+
 def _beta_from_lengthscale(ls):
     # exp(-d^2 / l^2) = exp(-beta d^2) with beta = l^-2, kept in torch so the lengthscale stays differentiable for the GP fit
     ls = ls.double().reshape(())

@@ -1407,6 +1407,173 @@ def flat_matern_kernel(x1, x2, lengthscale, nu):
     return _FlatMaternKernelFunction.apply(x1, x2, lengthscale, float(nu), x2 is x1)
 
 
+# ---- Matern / heat kernels of the affine-invariant SPD metric by random phase features (csrc/spd_ai_spectral.hip) ----
+# a(Z) = 2 log diag chol(Z);  rho_k = (d + 1 - 2k) / 4;  for feature l with spectral point lam_l, weight w_l and Haar matrix H_l:
+# a_il = a(H_l^T X_i H_l),  F_i = [sqrt(w_l) exp(-rho . a_il) cos(lam_l . a_il) | ... sin ...],  k(X_i, Y_j) = <F_i, F_j> / (|F_i| |F_j|).
+
+
+def _spectral_nu(nu):
+    """nu as a float: positive, or math.inf for the heat kernel (ValueError otherwise)"""
+    import math
+    if isinstance(nu, bool) or not isinstance(nu, (int, float)) or not (nu > 0.0) or math.isnan(nu):
+        raise ValueError(f"nu must be a positive number or math.inf, got {nu!r}")
+    return float(nu)
+
+
+def _spectral_rho(d, device=None):
+    return (d - 1 - 2.0 * torch.arange(d, dtype=torch.float64, device=device)) / 4.0
+
+
+def spd_ai_spectral_base(dim, num_features, nu, seed):
+    """The lengthscale-independent random draw behind the features -> (e, gamma, H): numpy arrays (L, d), (L,) or None (nu = inf), (L, d, d).
+    Host only, numpy.random.Generator(PCG64(seed)), drawn in this order:
+      1. standard_normal((L, d, d)) = G;  e = eigvalsh((G + G^T) / 2), density prop. to prod |e_i - e_j| exp(-|e|^2 / 2);
+      2. Generator.permuted(e, axis=1): the d entries of every row in random order;
+      3. finite nu only: gamma(shape nu, scale 1, L);
+      4. standard_normal((L, d, d)) = Q R;  H = Q with its columns multiplied by sign(diag R): Haar on O(d)."""
+    import math
+    import numpy as np
+    nu = _spectral_nu(nu)
+    if not (isinstance(dim, int) and dim >= 2) or not (isinstance(num_features, int) and num_features >= 1):
+        raise ValueError(f"dim must be an integer >= 2 and num_features an integer >= 1, got {dim!r}, {num_features!r}")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    g = rng.standard_normal((num_features, dim, dim))
+    e = rng.permuted(np.linalg.eigvalsh(0.5 * (g + g.transpose(0, 2, 1))), axis=1)
+    gamma = None if math.isinf(nu) else rng.gamma(nu, 1.0, num_features)
+    q, r = np.linalg.qr(rng.standard_normal((num_features, dim, dim)))
+    return e, gamma, q * np.sign(np.diagonal(r, axis1=-2, axis2=-1))[:, None, :]
+
+
+def spd_ai_spectral_points(base, lengthscale, nu):
+    """(e, gamma, H) and a lengthscale kappa -> (lam (L, d), w (L,)), torch fp64 on the lengthscale's device, differentiable in the lengthscale:
+    lam = e / kappa (nu = inf) or e sqrt((nu / kappa^2 + |rho|^2 / 2) / gamma), |rho|^2 = d (d^2 - 1) / 48;
+    w = prod_{i<j} tanh(pi |lam_i - lam_j|) in (0, 1], the part of the Plancherel density the draw of e leaves out (an importance weight)."""
+    import math
+    nu = _spectral_nu(nu)
+    ls = lengthscale if torch.is_tensor(lengthscale) else torch.tensor(float(lengthscale), dtype=torch.float64)
+    if ls.numel() != 1:
+        raise RuntimeError("gabotorch_amd SPD kernels take a single lengthscale (batch_shape == ())")
+    ls = ls.double().reshape(())
+    e, gamma = (torch.as_tensor(t, dtype=torch.float64, device=ls.device) if t is not None else None for t in base[:2])
+    d = e.shape[-1]
+    if math.isinf(nu):
+        lam = e / ls
+    else:
+        lam = e * torch.sqrt((nu / (ls * ls) + d * (d * d - 1) / 96.0) / gamma).unsqueeze(-1)
+    i, j = torch.triu_indices(d, d, 1, device=ls.device)
+    w = torch.tanh(math.pi * (lam[:, i] - lam[:, j]).abs()).prod(-1)
+    return lam, w
+
+
+_phases_held = None
+
+
+def _spectral_phases(phases, dev, d):
+    """(L, d, d) -> the entry-major (d, d, L) copy on `dev` that the launches read (a wave's loads are contiguous), remembered for the last
+    tensor handed in: a kernel object calls with the same one every time"""
+    global _phases_held
+    if phases.dim() != 3 or phases.shape[-1] != d or phases.shape[-2] != d:
+        raise RuntimeError(f"phases must be (L, {d}, {d}), got {tuple(phases.shape)}")
+    key = (phases.data_ptr(), phases._version, tuple(phases.shape), phases.device, phases.dtype, dev)
+    if _phases_held is None or _phases_held[0] != key:
+        _phases_held = (key, _prep(phases.detach(), dev).permute(1, 2, 0).contiguous(), phases)      # (holding `phases` keeps its address its own)
+    return _phases_held[1]
+
+
+def _spectral_points_input(x, what):
+    if x.dim() != 2:
+        raise RuntimeError(f"{what}: x must be (N, d(d+1)/2) Mandel vectors (no batch dimensions), got {tuple(x.shape)}")
+    return _mandel_dim(x.shape[-1])
+
+
+def spd_ai_logdiag(x, phases):
+    """x (N, d(d+1)/2) Mandel vectors, phases (L, d, d) orthogonal matrices -> a (N, L, d), a[i, l] = 2 log diag chol(H_l^T X_i H_l): one
+    launch (gabo_spd_ai_logdiag), 2 <= d <= 10, no gradient.  N L d 8 bytes.  A NaN or non-SPD row gives NaN in its own rows of `a`."""
+    lib = _lib.load()
+    d = _spectral_points_input(x, "spd_ai_logdiag")
+    out_device = x.device
+    dev = _device_for(x, phases)
+    xc = _prep(x.detach(), dev).contiguous()
+    ht = _spectral_phases(phases, dev, d)
+    n, L = xc.shape[0], ht.shape[-1]
+    out = torch.empty(n, L, d, dtype=torch.float64, device=dev)
+    with _on(dev):
+        _lib.check(lib.gabo_spd_ai_logdiag(xc.data_ptr(), ht.data_ptr(), out.data_ptr(), n, L, d, _stream_ptr(dev)), "gabo_spd_ai_logdiag")
+    return _out(out, out_device)
+
+
+def _spectral_features_torch(a, lam, weight):
+    """the features from log-diagonals a (N, L, d) by element-wise torch operations: differentiable in a, lam and weight"""
+    d = a.shape[-1]
+    amp = torch.sqrt(weight) * torch.exp(-(a * _spectral_rho(d, a.device)).sum(-1))
+    theta = (a * lam).sum(-1)
+    f = torch.cat([amp * torch.cos(theta), amp * torch.sin(theta)], dim=-1)
+    return f / torch.sqrt((f * f).sum(-1, keepdim=True))
+
+
+def _spectral_logdiag_torch(x, phases):
+    """a(H^T X H) as a plain torch composition (torch.linalg.cholesky on N L matrices): differentiable in x, first order, slow"""
+    d = _mandel_dim(x.shape[-1])
+    r, c = torch.tril_indices(d, d, device=x.device)
+    order = torch.argsort((r - c) * d + c, stable=True)          # Mandel order: the diagonal, then sub-diagonal 1, 2, ...
+    r, c = r[order], c[order]
+    scale = torch.ones(len(r), dtype=x.dtype, device=x.device).masked_fill(r != c, 0.5 ** 0.5)
+    mat = torch.zeros(x.shape[:-1] + (d, d), dtype=x.dtype, device=x.device)
+    mat = mat.index_put((torch.arange(x.shape[0], device=x.device)[:, None], r[None, :], c[None, :]), x * scale)
+    mat = mat + torch.tril(mat, -1).transpose(-1, -2)
+    s = torch.einsum("lba,nbc,lcd->nlad", phases, mat, phases)
+    return 2.0 * torch.log(torch.diagonal(torch.linalg.cholesky(0.5 * (s + s.transpose(-1, -2))), dim1=-2, dim2=-1))
+
+
+def spd_ai_spectral_features(x, phases, lam, weight, logdiag=None):
+    """Normalised random phase features F (N, 2 L) of the points x (N, d(d+1)/2), |F_i| = 1, for phases (L, d, d), spectral points lam (L, d)
+    and weights (L,).  The cheapest route that supports the gradients asked for:
+      - nothing requires grad, no `logdiag`: ONE fused launch (gabo_spd_ai_spectral_features); the log-diagonals are never stored;
+      - `logdiag` (= spd_ai_logdiag(x, phases)) given: element-wise torch operations on it, differentiable in lam and weight (so in the
+        lengthscale they come from); x is not looked at;
+      - x requires grad: a plain torch composition through torch.linalg.cholesky of the N L matrices H^T X H - first order, and slow."""
+    if logdiag is not None:
+        return _spectral_features_torch(logdiag, lam.to(logdiag), weight.to(logdiag))
+    d = _spectral_points_input(x, "spd_ai_spectral_features")
+    if torch.is_grad_enabled() and x.requires_grad:
+        xd = x.double()
+        return _spectral_features_torch(_spectral_logdiag_torch(xd, phases.to(xd)), lam.to(xd), weight.to(xd))
+    if torch.is_grad_enabled() and (lam.requires_grad or weight.requires_grad):
+        return _spectral_features_torch(spd_ai_logdiag(x, phases).to(lam.device), lam.double(), weight.double())
+    lib = _lib.load()
+    out_device = x.device
+    dev = _device_for(x, phases, lam, weight)
+    xc = _prep(x.detach(), dev).contiguous()
+    ht = _spectral_phases(phases, dev, d)
+    n, L = xc.shape[0], ht.shape[-1]
+    lc, wc = _prep(lam.detach(), dev).contiguous(), _prep(weight.detach(), dev).contiguous()
+    if tuple(lc.shape) != (L, d) or tuple(wc.shape) != (L,):
+        raise RuntimeError(f"lam must be ({L}, {d}) and weight ({L},), got {tuple(lc.shape)} and {tuple(wc.shape)}")
+    out = torch.empty(n, 2 * L, dtype=torch.float64, device=dev)
+    with _on(dev):
+        _lib.check(lib.gabo_spd_ai_spectral_features(xc.data_ptr(), ht.data_ptr(), lc.data_ptr(), wc.data_ptr(), out.data_ptr(), n, L, d,
+                                                     _stream_ptr(dev)), "gabo_spd_ai_spectral_features")
+    return _out(out, out_device)
+
+
+def spd_ai_matern_kernel(x1, x2, phases, lam, weight, logdiag1=None, logdiag2=None, diag=False):
+    """k(x1_i, x2_j) = <F(x1_i), F(x2_j)> (N1, N2) with F = spd_ai_spectral_features (routes and gradients: see there): a Monte-Carlo
+    approximation, error O(1 / sqrt L), of the Riemannian Matern / heat kernel of the affine-invariant metric that is positive semi-definite for
+    every sample.  `x2 is x1`: one feature call, and the matrix is exactly symmetric with an exactly unit diagonal.  diag=True: the diagonal
+    (N1 == N2), exactly 1 when x2 is x1."""
+    f1 = spd_ai_spectral_features(x1, phases, lam, weight, logdiag=logdiag1)
+    if x2 is x1:
+        k = torch.mm(f1, f1.t())
+        dg = k.diagonal()
+        unit = dg / dg                      # exactly 1, or NaN for a row of NaN features
+        if diag:
+            return unit
+        k = 0.5 * (k + k.t())
+        return torch.where(torch.eye(k.shape[0], dtype=torch.bool, device=k.device), unit.unsqueeze(-1).expand_as(k), k)
+    f2 = spd_ai_spectral_features(x2, phases, lam, weight, logdiag=logdiag2).to(f1.device)
+    return (f1 * f2).sum(-1) if diag else torch.mm(f1, f2.t())
+
+
 def gp_acquisition(kstar, alpha, linv, linv_t, mean, outputscale, kxx, best_f, kind, maximize, out_sign=1.0, need_grad=True):
     """Fused GP posterior + acquisition on the strip kstar (R x n, base kernel values): -> (value R, d value / d kstar R x n or None).
     All tensors fp64 on one HIP device."""

@@ -354,6 +354,24 @@ int gabo_gp_mll_matern(const double* r, const double* y, int64_t n, double lengt
                        double mean, double* out, gabo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Random phase features of the Riemannian Matern / heat kernels of the affine-invariant metric on S^d_++ (csrc/spd_ai_spectral.hip; the
+ * construction for non-compact symmetric spaces of Azangulov et al. 2023).  For an SPD matrix Z, a(Z) = 2 log diag chol(Z) with the lower
+ * Cholesky factor; for feature l with its orthogonal matrix H_l, a_il = a(H_l^T X_i H_l): one order-d factorisation per (point, feature)
+ * pair, one lane each.  2 <= d <= 10 (GABO_ERR_DIM outside).
+ *   x_mandel: n x d(d+1)/2 Mandel vectors.
+ *   phases:   the L orthogonal matrices, ENTRY-MAJOR: H_l[r][c] at phases[(r * d + c) * L + l]  (d x d x L).
+ * gabo_spd_ai_logdiag: out[(i * L + l) * d + k] = a_k(H_l^T X_i H_l), n x L x d.
+ * gabo_spd_ai_spectral_features: lam L x d (the spectral points), weight L (importance weights w_l >= 0); with rho_k = (d + 1 - 2k) / 4,
+ *   k = 1 .. d:  A_il = exp(-rho . a_il), theta_il = lam_l . a_il, F_i = [sqrt(w_l) A_il cos theta_il | sqrt(w_l) A_il sin theta_il],
+ *   out = F_i / ||F_i||, n x 2L.  `a` is never stored.  The row's sum of squares is formed in one fixed order.
+ * The bits of a_il depend on X_i and H_l alone, those of out row i on X_i, phases, lam and weight alone (not on n or the other points).
+ * A NaN or non-SPD X_i (a Cholesky pivot that is not > 0) gives NaN in every output of row i and nowhere else; like gabo_spd_logm_mandel
+ * the entries take no status word and report nothing. */
+int gabo_spd_ai_logdiag(const double* x_mandel, const double* phases, double* out, int64_t n, int64_t L, int d, gabo_stream_t stream);
+int gabo_spd_ai_spectral_features(const double* x_mandel, const double* phases, const double* lam, const double* weight, double* out,
+                                  int64_t n, int64_t L, int d, gabo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Extreme eigenvalues of the kernel matrices of a kernel-parameter study, all (point set, parameter) pairs in one launch
  * (examples/kernels/spd/spd_gaussian_kernel_parameters.py:84-125 and examples/kernels/sphere/sphere_gaussian_kernel_parameters.py:62-112:
  * per pair one kernel.forward and one np.linalg.eig on the host, of which the minimum is kept).
