@@ -4,6 +4,8 @@ torch is used for device memory and stream ownership only; every number is produ
 Inputs living on the CPU are moved to the GPU, computed there and moved back (the reference's examples build CPU
 tensors); without a GPU every call raises - there is no CPU implementation in this package.
 """
+import math
+
 import torch
 
 from . import _lib, _status
@@ -38,7 +40,7 @@ _NO_CTX = _NoCtx()
 
 
 def _on(device):
-    """`with _on(dev):` = `with _on(dev):` when dev is not the current device, nothing otherwise (the guard object costs ~8 us)"""
+    """`with _on(dev):` = `with torch.cuda.device(dev):` when dev is not the current device, nothing otherwise (the guard object costs ~8 us)"""
     idx = device.index if isinstance(device, torch.device) else torch.device(device).index
     return _NO_CTX if (idx is None or idx == torch.cuda.current_device()) else torch.cuda.device(idx)
 
@@ -46,24 +48,88 @@ def _on(device):
 def _flatten_batch(x, tail_dims):
     """(..., tail) -> (tensor2d_or_3d contiguous, batch, batch_stride_in_elements).  A batch produced by
     `.expand()` (all batch strides 0) is passed as ONE shared set with batch stride 0."""
-    bshape = x.shape[:-tail_dims]
-    nb = 1
-    for s in bshape:
-        nb *= s
+    shape = x.shape                   # (every read of .shape builds a torch.Size: once)
+    bshape = shape[:-tail_dims]
+    nb = math.prod(bshape)
     if len(bshape) > 0 and nb > 1 and all(st == 0 for st, sz in zip(x.stride()[:len(bshape)], bshape) if sz > 1):
         base = x[(0,) * len(bshape)].contiguous()
         return base, nb, 0
-    xc = x.contiguous()
-    tail = 1
-    for s in x.shape[-tail_dims:]:
-        tail *= s
-    return xc, nb, tail
+    return x.contiguous(), nb, math.prod(shape[-tail_dims:])
 
 
 def _prep(x, device):
     if x.dtype != torch.float64:
         x = x.double()
     return x.to(device)
+
+
+def _ptr(t):
+    """the address of an optional tensor"""
+    return None if t is None else t.data_ptr()
+
+
+def _workspace(wsb, dev):
+    """`wsb` bytes of device scratch as fp64 words (never an empty tensor: its address is handed over even when the entry asks for nothing)"""
+    return torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
+
+
+def _pinned(n):
+    """n fp64 words of page-locked host memory"""
+    return torch.empty(n, dtype=torch.float64).pin_memory()
+
+
+def _dense(x, *others):
+    """One tensor in, one tensor of the same batch out: -> (the caller's device, the launch device, x as contiguous fp64 there).
+    `others`: further tensor arguments that may decide the launch device."""
+    dev = _device_for(x, *others)
+    return x.device, dev, _prep(x, dev).contiguous()
+
+
+def _check_two_sets(x1, x2, suffix=""):
+    sh1, sh2 = x1.shape, x2.shape
+    if sh1[:-2] != sh2[:-2] or sh1[-1] != sh2[-1]:
+        raise RuntimeError(f"batch/feature shapes differ: {tuple(sh1)} vs {tuple(sh2)}{suffix}")
+
+
+_NO_BROADCASTING = " (no broadcasting, as in the reference)"
+
+
+def _two_sets(x1, x2, others=(), one_set=False):
+    """The prologue of every launch on two point sets x1 (..., N1, f), x2 (..., N2, f) of one batch shape:
+    -> (launch device, x1 flattened, x2 flattened, nb, N1, N2, batch stride of x1, of x2, batch shape), the sets as _flatten_batch lays them
+    out (an expand()ed set once, stride 0).  `others`: further tensor arguments that may decide the device.
+    one_set: x2 is x1 and the entry promises the same address for both."""
+    dev = _device_for(x1, x2, *others)
+    a2, nb, s1 = _flatten_batch(_prep(x1, dev), 2)
+    b2, _, s2 = (a2, nb, s1) if one_set else _flatten_batch(_prep(x2, dev), 2)
+    sh1 = x1.shape
+    return dev, a2, b2, nb, sh1[-2], x2.shape[-2], s1, s2, sh1[:-2]
+
+
+def _gram_sets(x1, x2, suffix="", one_set=False, diag=False):
+    """_two_sets behind the shape check, with the fp64 output (..., N1, N2) - diag: (..., N, 1) - in place of the batch shape"""
+    _check_two_sets(x1, x2, suffix)
+    dev, a2, b2, nb, n1, n2, s1, s2, bshape = _two_sets(x1, x2, (), one_set)
+    if diag and n1 != n2:
+        raise RuntimeError("diag=True needs x1 and x2 of the same length")
+    return dev, a2, b2, nb, n1, n2, s1, s2, torch.empty(bshape + ((n1, 1) if diag else (n1, n2)), dtype=torch.float64, device=dev)
+
+
+def _wrt_roles(wrt, a2, b2, n1, n2, s1, s2, go_si, go_sj):
+    """A gradient with respect to x2 is the one with respect to x1 of the launch with the two sets exchanged and grad_out read transposed:
+    -> (first set, second set, their sizes, their batch strides, row and column stride of grad_out, sign).  The sign goes with the epsilon the
+    flat metrics add to x1 - x2 (frobenius_pairwise); the affine-invariant distance is symmetric and ignores it."""
+    if wrt == 1:
+        return a2, b2, n1, n2, s1, s2, go_si, go_sj, 1.0
+    return b2, a2, n2, n1, s2, s1, go_sj, go_si, -1.0
+
+
+def _sum_shared_first_set(gx, nb, sf):
+    """The flat gradients with the first set handed over as ONE expand()ed set (batch stride 0): the launch wrote one slice per batch entry;
+    the caller gets their sum, expanded like the input."""
+    if sf == 0 and nb > 1:
+        return gx.reshape((nb,) + gx.shape[-2:]).sum(0).expand(gx.shape)
+    return gx
 
 
 def _require(dev, **tensors):
@@ -99,32 +165,45 @@ def _mandel_dim(dv):
     return d
 
 
+# The one scalar parameter of a kernel (beta, lengthscale): a Python number or a one-element tensor at the entry, an fp64 tensor for the
+# autograd Function (a tensor keeps its shape), whose gradient goes back in the shape and on the device the parameter came in.
+def _scalar_param(value, refusal):
+    if torch.is_tensor(value):
+        if value.numel() != 1:
+            raise RuntimeError(refusal)
+        return value.double()
+    return torch.tensor(float(value), dtype=torch.float64)
+
+
+def _note_param(ctx, param):
+    ctx.param_like = (param.shape, param.device) if torch.is_tensor(param) else (None, None)
+
+
+def _param_grad(ctx, grad):
+    shape, device = ctx.param_like
+    return grad.reshape(shape).to(device)
+
+
+_ONE_SPD_LENGTHSCALE = "gabotorch_amd SPD kernels take a single lengthscale (batch_shape == ())"
+
+
 def spd_ai_pairwise(x1, x2, beta=1.0, mode=_lib.GABO_OUT_GAUSSIAN, symmetric=False, return_dist=False):
     """x1 (..., N1, d_vec), x2 (..., N2, d_vec) Mandel vectors -> (..., N1, N2) on x1's device.
     return_dist=True also returns the distance matrix written by the same launch."""
     lib = _lib.load()
-    if x1.shape[:-2] != x2.shape[:-2] or x1.shape[-1] != x2.shape[-1]:
-        raise RuntimeError(f"batch/feature shapes differ: {tuple(x1.shape)} vs {tuple(x2.shape)} (no broadcasting, as in the reference)")
     out_device = x1.device
-    dev = _device_for(x1, x2)
-    a, b = _prep(x1, dev), _prep(x2, dev)
-    d = _mandel_dim(a.shape[-1])
-    n1, n2 = a.shape[-2], b.shape[-2]
-    bshape = a.shape[:-2]
-    a2, nb, s1 = _flatten_batch(a, 2)
-    b2, _, s2 = _flatten_batch(b, 2)
-    out = torch.empty(bshape + (n1, n2), dtype=torch.float64, device=dev)
+    dev, a2, b2, nb, n1, n2, s1, s2, out = _gram_sets(x1, x2, _NO_BROADCASTING)
+    d = _mandel_dim(a2.shape[-1])
     dist = torch.empty_like(out) if return_dist else None
     if out.numel() == 0:
         return (out.to(out_device), dist.to(out_device)) if return_dist else out.to(out_device)
     wsb = lib.gabo_spd_ai_workspace_bytes(nb, n1, n2, d)
-    ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
+    ws = _workspace(wsb, dev)
     status = _status_word(dev)
     flags = int(mode) | (_lib.GABO_SYMMETRIC if symmetric else 0)
     with _on(dev):
-        rc = lib.gabo_spd_ai_pairwise(a2.data_ptr(), b2.data_ptr(), out.data_ptr(), dist.data_ptr() if return_dist else None,
-                                      nb, n1, n2, d, s1, s2, float(beta), flags, ws.data_ptr(), wsb, status.data_ptr(),
-                                      _stream_ptr(dev))
+        rc = lib.gabo_spd_ai_pairwise(a2.data_ptr(), b2.data_ptr(), out.data_ptr(), _ptr(dist), nb, n1, n2, d, s1, s2, float(beta), flags,
+                                      ws.data_ptr(), wsb, status.data_ptr(), _stream_ptr(dev))
     _check_launch(rc, status, "gabo_spd_ai_pairwise")
     if return_dist:
         return _out(out, out_device), dist.to(out_device)
@@ -136,24 +215,15 @@ def spd_ai_backward(x1, x2, grad_out, beta=1.0, mode=_lib.GABO_OUT_GAUSSIAN, wrt
     grad_out (..., N1, N2).  Returns a tensor shaped like the differentiated argument."""
     lib = _lib.load()
     out_device = (x1 if wrt == 1 else x2).device
-    dev = _device_for(x1, x2, grad_out)
-    a, b, g = _prep(x1, dev), _prep(x2, dev), _prep(grad_out, dev).contiguous()
-    d = _mandel_dim(a.shape[-1])
-    n1, n2 = a.shape[-2], b.shape[-2]
-    bshape = a.shape[:-2]
-    a2, nb, s1 = _flatten_batch(a, 2)
-    b2, _, s2 = _flatten_batch(b, 2)
-    if wrt == 1:
-        first, second, m1, m2, sf, ss = a2, b2, n1, n2, s1, s2
-        go_si, go_sj = n2, 1
-    else:       # exchange the roles of the two sets and read grad_out transposed
-        first, second, m1, m2, sf, ss = b2, a2, n2, n1, s2, s1
-        go_si, go_sj = 1, n2
-    gx = torch.zeros(bshape + (m1, a.shape[-1]), dtype=torch.float64, device=dev)
+    dev, a2, b2, nb, n1, n2, s1, s2, bshape = _two_sets(x1, x2, (grad_out,))
+    g = _prep(grad_out, dev).contiguous()
+    d = _mandel_dim(a2.shape[-1])
+    first, second, m1, m2, sf, ss, go_si, go_sj, _ = _wrt_roles(wrt, a2, b2, n1, n2, s1, s2, n2, 1)
+    gx = torch.zeros(bshape + (m1, a2.shape[-1]), dtype=torch.float64, device=dev)
     if gx.numel() == 0 or m2 == 0:
         return _out(gx, out_device)
     wsb = lib.gabo_spd_ai_workspace_bytes(nb, m1, m2, d)
-    ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
+    ws = _workspace(wsb, dev)
     status = _status_word(dev)
     with _on(dev):
         rc = lib.gabo_spd_ai_backward(first.data_ptr(), second.data_ptr(), g.data_ptr(), gx.data_ptr(), nb, m1, m2, d, sf, ss,
@@ -172,30 +242,25 @@ def spd_ai_backward2(x1, x2, grad_out, u, beta=1.0, mode=_lib.GABO_OUT_GAUSSIAN,
     mixed = d <spd_ai_backward(x1, x2, grad_out), u> / d x2 (shaped like x2, or None)."""
     lib = _lib.load()
     out_device = x1.device
-    dev = _device_for(x1, x2, grad_out, u)
-    a, b = _prep(x1, dev), _prep(x2, dev)
+    dev, a2, b2, nb, n1, n2, s1, s2, bshape = _two_sets(x1, x2, (grad_out, u))
     g, uu = _prep(grad_out, dev).contiguous(), _prep(u, dev).contiguous()
-    if uu.shape != a.shape:
-        raise RuntimeError(f"direction {tuple(uu.shape)} is not shaped like x1 {tuple(a.shape)}")
-    d = _mandel_dim(a.shape[-1])
-    n1, n2 = a.shape[-2], b.shape[-2]
-    bshape = a.shape[:-2]
-    a2, nb, s1 = _flatten_batch(a, 2)
-    b2, _, s2 = _flatten_batch(b, 2)
+    if uu.shape != x1.shape:
+        raise RuntimeError(f"direction {tuple(uu.shape)} is not shaped like x1 {tuple(x1.shape)}")
+    dv = a2.shape[-1]
+    d = _mandel_dim(dv)
     if s1 == 0 and nb > 1:                       # an expand()ed x1 with per-batch directions: give every batch its own copy
-        a2, s1 = a.contiguous().reshape(nb, n1, -1), n1 * a.shape[-1]
-    hv = torch.zeros(bshape + (n1, a.shape[-1]), dtype=torch.float64, device=dev)
+        a2, s1 = a2.expand(nb, n1, dv).contiguous(), n1 * dv
+    hv = torch.zeros(bshape + (n1, dv), dtype=torch.float64, device=dev)
     dg = torch.zeros(bshape + (n1, n2), dtype=torch.float64, device=dev) if want_dgrad_out else None
-    mx = torch.zeros(bshape + (n2, a.shape[-1]), dtype=torch.float64, device=dev) if want_mixed else None
+    mx = torch.zeros(bshape + (n2, dv), dtype=torch.float64, device=dev) if want_mixed else None
     if hv.numel() == 0 or n2 == 0:
         return _out(hv, out_device), (None if dg is None else dg.to(out_device)), (None if mx is None else mx.to(x2.device))
     wsb = lib.gabo_spd_ai_backward2_workspace_bytes(nb, n1, n2, d)
-    ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
+    ws = _workspace(wsb, dev)
     status = _status_word(dev)
     with _on(dev):
-        rc = lib.gabo_spd_ai_backward2(a2.data_ptr(), b2.data_ptr(), g.data_ptr(), uu.data_ptr(), hv.data_ptr(), None if dg is None else dg.data_ptr(),
-                                       None if mx is None else mx.data_ptr(), nb, n1, n2, d, s1, s2, n1 * n2, n2, 1, float(beta), int(mode),
-                                       ws.data_ptr(), wsb, status.data_ptr(), _stream_ptr(dev))
+        rc = lib.gabo_spd_ai_backward2(a2.data_ptr(), b2.data_ptr(), g.data_ptr(), uu.data_ptr(), hv.data_ptr(), _ptr(dg), _ptr(mx), nb, n1, n2, d,
+                                       s1, s2, n1 * n2, n2, 1, float(beta), int(mode), ws.data_ptr(), wsb, status.data_ptr(), _stream_ptr(dev))
     _lib.check(rc, "gabo_spd_ai_backward2")
     _raise_if_not_spd(status, "gabo_spd_ai_backward2")
     # (x2 as one expand()ed set: mx stays per batch entry, like spd_ai_backward's result - ExpandBackward does the sum)
@@ -215,7 +280,7 @@ class _SpdAiGradFunction(torch.autograd.Function):
         bval = float(beta)
         ctx.save_for_backward(x1, x2, grad_out)
         ctx.bval, ctx.mode, ctx.wrt = bval, mode, wrt
-        ctx.beta_shape, ctx.beta_device = beta.shape, beta.device
+        _note_param(ctx, beta)
         return spd_ai_backward(x1, x2, grad_out, bval, mode, wrt=wrt).to((x1 if wrt == 1 else x2).dtype)
 
     @staticmethod
@@ -239,7 +304,7 @@ class _SpdAiGradFunction(torch.autograd.Function):
                 gb = (grad_out.to(dg.device) * dg * (1.0 / ctx.bval - w)).sum()
             else:
                 gb = torch.zeros((), dtype=torch.float64, device=grad_out.device)
-            gb = gb.reshape(ctx.beta_shape).to(ctx.beta_device)
+            gb = _param_grad(ctx, gb)
         return (d1.to(x1.dtype) if need1 else None), (d2.to(x2.dtype) if need2 else None), (dg.to(grad_out.dtype) if needg else None), gb, None, None
 
 
@@ -260,8 +325,7 @@ class _SpdAiKernelFunction(torch.autograd.Function):
             same = x1.data_ptr() == x2.data_ptr() and x1.shape == x2.shape and x1.stride() == x2.stride() and x1.dim() == 2
             out = spd_ai_pairwise(x1, x2, bval, mode, symmetric=same)
         ctx.bval, ctx.mode = bval, mode
-        ctx.beta_shape = beta.shape if torch.is_tensor(beta) else None
-        ctx.beta_device = beta.device if torch.is_tensor(beta) else None
+        _note_param(ctx, beta)
         return out
 
     @staticmethod
@@ -297,37 +361,22 @@ class _SpdAiKernelFunction(torch.autograd.Function):
                     gb = -(go * out * dist * dist).sum()      # dK/dbeta = -d^2 K
                 else:
                     gb = -(go * out * dist).sum()             # dK/dbeta = -d K
-            gb = gb.reshape(ctx.beta_shape).to(ctx.beta_device)
+            gb = _param_grad(ctx, gb)
         return g1, g2, gb, None
 
 
 def spd_ai_kernel(x1, x2, beta, mode=_lib.GABO_OUT_GAUSSIAN):
     """Differentiable entry point used by the kernel classes.  beta: python float or a one-element tensor."""
-    if torch.is_tensor(beta):
-        if beta.numel() != 1:
-            raise RuntimeError("gabotorch_amd SPD kernels take a single beta (batch_shape == ()), as every reference example does")
-        beta = beta.double()
-    else:
-        beta = torch.tensor(float(beta), dtype=torch.float64)
+    beta = _scalar_param(beta, "gabotorch_amd SPD kernels take a single beta (batch_shape == ()), as every reference example does")
     return _SpdAiKernelFunction.apply(x1, x2, beta, int(mode))
 
 
 def sphere_pairwise(x1, x2, beta=1.0, mode=_lib.GABO_OUT_GAUSSIAN, diag=False, symmetric=False):
     """x1 (..., N1, dim), x2 (..., N2, dim) -> (..., N1, N2)   [diag: (..., N, 1)]."""
     lib = _lib.load()
-    if x1.shape[:-2] != x2.shape[:-2] or x1.shape[-1] != x2.shape[-1]:
-        raise RuntimeError(f"batch/feature shapes differ: {tuple(x1.shape)} vs {tuple(x2.shape)}")
     out_device = x1.device
-    dev = _device_for(x1, x2)
-    a, b = _prep(x1, dev), _prep(x2, dev)
-    dim = a.shape[-1]
-    n1, n2 = a.shape[-2], b.shape[-2]
-    if diag and n1 != n2:
-        raise RuntimeError("diag=True needs x1 and x2 of the same length")
-    bshape = a.shape[:-2]
-    a2, nb, s1 = _flatten_batch(a, 2)
-    b2, _, s2 = _flatten_batch(b, 2)
-    out = torch.empty(bshape + ((n1, 1) if diag else (n1, n2)), dtype=torch.float64, device=dev)
+    dev, a2, b2, nb, n1, n2, s1, s2, out = _gram_sets(x1, x2, diag=diag)
+    dim = a2.shape[-1]
     if out.numel() == 0:
         return _out(out, out_device)
     flags = int(mode) | (_lib.GABO_SYMMETRIC if symmetric and not diag else 0)
@@ -338,7 +387,7 @@ def sphere_pairwise(x1, x2, beta=1.0, mode=_lib.GABO_OUT_GAUSSIAN, diag=False, s
         if lib.gabo_sphere_pairwise_uses_ktable(nb, n1, n2, dim, float(beta), flags, 1 if diag else 0) and not torch.cuda.is_current_stream_capturing():
             ktable = _sphere_ktable(lib, dev, stream, float(beta))
         rc = lib.gabo_sphere_pairwise_cached(a2.data_ptr(), b2.data_ptr(), out.data_ptr(), nb, n1, n2, dim, s1, s2, float(beta), flags,
-                                             1 if diag else 0, None if ktable is None else ktable.data_ptr(), stream)
+                                             1 if diag else 0, _ptr(ktable), stream)
     _lib.check(rc, "gabo_sphere_pairwise")
     return _out(out, out_device)
 
@@ -365,9 +414,7 @@ def _sphere_ktable(lib, dev, stream, beta):
 def sphere_from_inner(inner, beta, mode, order):
     """Element-wise f^(order)(c) on an inner-product tensor (any shape)."""
     lib = _lib.load()
-    out_device = inner.device
-    dev = _device_for(inner)
-    c = _prep(inner, dev).contiguous()
+    out_device, dev, c = _dense(inner)
     out = torch.empty_like(c)
     with _on(dev):
         _lib.check(lib.gabo_sphere_from_inner(c.data_ptr(), out.data_ptr(), c.numel(), float(beta), int(mode), int(order),
@@ -384,8 +431,7 @@ class _SphereFromInner(torch.autograd.Function):
         out = sphere_from_inner(c, bval, mode, order)
         ctx.save_for_backward(c, out)
         ctx.bval, ctx.mode, ctx.order = bval, mode, order
-        ctx.beta_shape = beta.shape if torch.is_tensor(beta) else None
-        ctx.beta_device = beta.device if torch.is_tensor(beta) else None
+        _note_param(ctx, beta)
         return out
 
     @staticmethod
@@ -407,7 +453,7 @@ class _SphereFromInner(torch.autograd.Function):
                     gb = -(g * out * th).sum()
                 else:
                     gb = torch.zeros((), dtype=g.dtype, device=g.device)
-                gb = gb.reshape(ctx.beta_shape).to(ctx.beta_device)
+                gb = _param_grad(ctx, gb)
         return gc, gb, None, None
 
 
@@ -415,12 +461,7 @@ def sphere_kernel(x1, x2, beta, mode=_lib.GABO_OUT_GAUSSIAN, diag=False):
     """Differentiable entry point of the sphere kernels.  Without autograd: one fused pairwise launch.  With autograd: the
     inner products are a plain batched GEMM (torch.matmul -> rocBLAS) followed by the element-wise HIP kernel, which keeps the
     expression differentiable twice in x1/x2."""
-    if torch.is_tensor(beta):
-        if beta.numel() != 1:
-            raise RuntimeError("gabotorch_amd sphere kernels take a single beta (batch_shape == ())")
-        beta = beta.double()
-    else:
-        beta = torch.tensor(float(beta), dtype=torch.float64)
+    beta = _scalar_param(beta, "gabotorch_amd sphere kernels take a single beta (batch_shape == ())")
     need = torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad or beta.requires_grad)
     if not need:
         # (no automatic GABO_SYMMETRIC here: the sphere launch is so short that the mirror pass costs more than it saves)
@@ -476,7 +517,6 @@ def sphere_matern_coefficients_and_derivative(dim, lengthscale, nu, num_levels):
 
 
 def _sphere_matern_arguments(dim, lengthscale, nu, num_levels):
-    import math
     dim, L = int(dim), int(num_levels)
     kappa, nu = float(lengthscale), float(nu)
     if dim < 2:
@@ -496,8 +536,6 @@ _sphere_level_logm = {}
 def _sphere_matern_weights(dim, kappa, nu, L):
     """(p_n, Phi'(lambda_n) / Phi(lambda_n) in kappa, d) of sphere_matern_coefficients for validated arguments.  The log multiplicities
     log m_n - exact integers, a Python loop - do not depend on kappa: kept per (dim, num_levels)."""
-    import math
-
     import numpy as np
     d = dim - 1
     n = np.arange(L + 1, dtype=np.float64)
@@ -550,9 +588,7 @@ def _zonal_coeff(coeff):
 def sphere_zonal_from_inner(inner, coeff, series_dim):
     """Element-wise sum_k coeff[k] P_k(c) on an inner-product tensor (any shape); coeff: host float64 (see sphere_matern_coefficients)."""
     lib = _lib.load()
-    out_device = inner.device
-    dev = _device_for(inner)
-    c = _prep(inner, dev).contiguous()
+    out_device, dev, c = _dense(inner)
     out = torch.empty_like(c)
     a, ptr, na = _zonal_coeff(coeff)
     with _on(dev):
@@ -564,19 +600,9 @@ def sphere_zonal_from_inner(inner, coeff, series_dim):
 def sphere_zonal_pairwise(x1, x2, coeff, series_dim, diag=False, symmetric=False):
     """x1 (..., N1, dim), x2 (..., N2, dim) -> (..., N1, N2)   [diag: (..., N, 1)]:  sum_k coeff[k] P_k(<x1_i, x2_j>) in one launch."""
     lib = _lib.load()
-    if x1.shape[:-2] != x2.shape[:-2] or x1.shape[-1] != x2.shape[-1]:
-        raise RuntimeError(f"batch/feature shapes differ: {tuple(x1.shape)} vs {tuple(x2.shape)}")
     out_device = x1.device
-    dev = _device_for(x1, x2)
-    a, b = _prep(x1, dev), _prep(x2, dev)
-    dim = a.shape[-1]
-    n1, n2 = a.shape[-2], b.shape[-2]
-    if diag and n1 != n2:
-        raise RuntimeError("diag=True needs x1 and x2 of the same length")
-    bshape = a.shape[:-2]
-    a2, nb, s1 = _flatten_batch(a, 2)
-    b2, _, s2 = _flatten_batch(b, 2)
-    out = torch.empty(bshape + ((n1, 1) if diag else (n1, n2)), dtype=torch.float64, device=dev)
+    dev, a2, b2, nb, n1, n2, s1, s2, out = _gram_sets(x1, x2, diag=diag)
+    dim = a2.shape[-1]
     ca, ptr, na = _zonal_coeff(coeff)
     if out.numel() == 0:
         return _out(out, out_device)
@@ -599,8 +625,7 @@ class _SphereMaternFromInner(torch.autograd.Function):
         out = sphere_zonal_from_inner(c, coeff, sd)
         ctx.save_for_backward(c)
         ctx.lval, ctx.spec, ctx.order = lval, (dim, nu, num_levels), order
-        ctx.ls_shape = lengthscale.shape if torch.is_tensor(lengthscale) else None
-        ctx.ls_device = lengthscale.device if torch.is_tensor(lengthscale) else None
+        _note_param(ctx, lengthscale)
         return out
 
     @staticmethod
@@ -617,7 +642,7 @@ class _SphereMaternFromInner(torch.autograd.Function):
                 raise RuntimeError("mixed x/lengthscale second derivatives of the sphere kernels are not provided")
             with torch.no_grad():
                 coeff, sd = sphere_matern_coefficients(dim, ctx.lval, nu, num_levels, 0, wrt_lengthscale=True)
-                gl = (g * sphere_zonal_from_inner(c, coeff, sd)).sum().reshape(ctx.ls_shape).to(ctx.ls_device)
+                gl = _param_grad(ctx, (g * sphere_zonal_from_inner(c, coeff, sd)).sum())
         return gc, gl, None, None, None, None
 
 
@@ -625,12 +650,7 @@ def sphere_matern_kernel(x1, x2, lengthscale, nu, num_levels, diag=False):
     """Differentiable entry point of the Riemannian Matern kernel on the sphere (nu = math.inf: heat kernel), shaped like sphere_kernel.
     Without autograd: one fused launch (the symmetric one when x1 is x2).  With autograd: the inner products are a plain batched GEMM followed
     by the element-wise series, differentiable twice in x1 / x2 and once in the lengthscale."""
-    if torch.is_tensor(lengthscale):
-        if lengthscale.numel() != 1:
-            raise RuntimeError("gabotorch_amd sphere kernels take a single lengthscale (batch_shape == ())")
-        lengthscale = lengthscale.double()
-    else:
-        lengthscale = torch.tensor(float(lengthscale), dtype=torch.float64)
+    lengthscale = _scalar_param(lengthscale, "gabotorch_amd sphere kernels take a single lengthscale (batch_shape == ())")
     dim = x1.shape[-1]
     need = torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad or lengthscale.requires_grad)
     if not need:
@@ -648,13 +668,9 @@ def sphere_matern_kernel(x1, x2, lengthscale, nu, num_levels, diag=False):
 def mandel_to_matrix(vec):
     """(..., d_vec) -> (..., d, d)."""
     lib = _lib.load()
-    out_device = vec.device
-    dev = _device_for(vec)
-    v = _prep(vec, dev).contiguous()
+    out_device, dev, v = _dense(vec)
     dv = v.shape[-1]
-    d = int((-1.0 + (1.0 + 8.0 * dv) ** 0.5) / 2.0)
-    if d * (d + 1) // 2 != dv:
-        raise RuntimeError(f"last dimension {dv} is not d(d+1)/2")
+    d = _mandel_dim(dv)
     n = v.numel() // dv if dv else 0
     out = torch.empty(v.shape[:-1] + (d, d), dtype=torch.float64, device=dev)
     with _on(dev):
@@ -665,9 +681,7 @@ def mandel_to_matrix(vec):
 def matrix_to_mandel(mat):
     """(..., d, d) -> (..., d_vec), averaging the two triangles."""
     lib = _lib.load()
-    out_device = mat.device
-    dev = _device_for(mat)
-    m = _prep(mat, dev).contiguous()
+    out_device, dev, m = _dense(mat)
     d = m.shape[-1]
     if m.shape[-2] != d:
         raise RuntimeError("last two dimensions must be square")
@@ -715,9 +729,8 @@ def spd_manifold_op(op, a, b=None, c=None, e=None, want_grad=False):
     elif want_grad and matfun:
         out2 = torch.empty(shape[:-2] + (d * d + d,), dtype=torch.float64, device=dev)      # V and the eigenvalues, for the backward
     status = _status_word(dev)
-    ptr = lambda t_: None if t_ is None else t_.data_ptr()   # noqa: E731
     with _on(dev):
-        rc = lib.gabo_spd_manifold_op(int(op), ptr(A), ptr(B), ptr(C), ptr(E), out.data_ptr(), ptr(out2), n, d, status.data_ptr(),
+        rc = lib.gabo_spd_manifold_op(int(op), _ptr(A), _ptr(B), _ptr(C), _ptr(E), out.data_ptr(), _ptr(out2), n, d, status.data_ptr(),
                                       _stream_ptr(dev))
     _check_launch(rc, status, "gabo_spd_manifold_op")
     if out2 is not None:
@@ -789,7 +802,7 @@ class NestedSpdReconstruction:
             nV, nC, nK = self.sizes
             npar = nV + nC + nK
             ws = max(int(lib.gabo_nested_spd_reconstruction_workspace_bytes(P, max(self.N, 1), self.D, self.d)), 16)
-            host_in, host_out = torch.empty(P * npar, dtype=torch.float64).pin_memory(), torch.empty(P * (1 + npar), dtype=torch.float64).pin_memory()
+            host_in, host_out = _pinned(P * npar), _pinned(P * (1 + npar))
             dev_in = torch.empty(P * npar, dtype=torch.float64, device=self.device)
             dev_out = torch.empty(P * (1 + npar), dtype=torch.float64, device=self.device)
             o1, o2, o3 = P, P + P * nV, P + P * (nV + nC)
@@ -804,10 +817,9 @@ class NestedSpdReconstruction:
     def launch(self, v, c, k, cost, gv, gc, gk, P, ws):
         """Raw launch on contiguous fp64 device tensors (gv = gc = gk = None: values only)."""
         lib = _lib.load()
-        ptr = lambda t_: None if t_ is None else t_.data_ptr()   # noqa: E731
         with torch.cuda.device(self.device):
             _lib.check(lib.gabo_nested_spd_reconstruction(self.data.data_ptr(), self.y.data_ptr(), self.sqrt_y.data_ptr(), self.w.data_ptr(),
-                                                          v.data_ptr(), c.data_ptr(), k.data_ptr(), cost.data_ptr(), ptr(gv), ptr(gc), ptr(gk), None,
+                                                          v.data_ptr(), c.data_ptr(), k.data_ptr(), cost.data_ptr(), _ptr(gv), _ptr(gc), _ptr(gk), None,
                                                           None, P, self.N, self.D, self.d, self.metric, ws.data_ptr(), ws.numel(),
                                                           _stream_ptr(self.device)),
                        "gabo_nested_spd_reconstruction")
@@ -859,7 +871,7 @@ class NestedSpdReconstruction:
             dev_bytes, pin_doubles = ctypes.c_size_t(0), ctypes.c_size_t(0)
             lib.gabo_nested_spd_reconstruction_solve_workspace_bytes(self.N, self.D, self.d, ctypes.byref(dev_bytes), ctypes.byref(pin_doubles))
             ent = self._buffers["solve"] = dict(ws=torch.empty(max(dev_bytes.value, 16), dtype=torch.uint8, device=self.device),
-                                                pinned=torch.empty(pin_doubles.value, dtype=torch.float64).pin_memory(),
+                                                pinned=_pinned(pin_doubles.value),
                                                 w_host=np.ascontiguousarray(self.w.cpu().numpy(), dtype=np.float64))
         v, c, u = (np.array(a, dtype=np.float64, order="C") for a in (V, C, unit))
         r = np.array([float(np.asarray(raw).reshape(-1)[0])], dtype=np.float64)
@@ -974,7 +986,7 @@ def nested_spd_extreme_eigenvalues(y, w, p, x0, want_grad=False):
     grad = torch.empty(Y.shape[:-2] + (2, d, d), dtype=torch.float64, device=dev) if want_grad else None
     with _on(dev):
         _lib.check(lib.gabo_nested_spd_extreme_eigenvalues(Y.data_ptr(), w.data_ptr(), p.data_ptr(), x0.data_ptr(), lam.data_ptr(),
-                                                           None if grad is None else grad.data_ptr(), R, D, d, _stream_ptr(dev)),
+                                                           _ptr(grad), R, D, d, _stream_ptr(dev)),
                    "gabo_nested_spd_extreme_eigenvalues")
     return (lam, grad) if want_grad else lam
 
@@ -1050,75 +1062,48 @@ def spd_project_diff(x_mandel, w):
     return spd_project(x_mandel, w)
 
 
-def nested_spd_gram(x1, x2, w, beta, metric=_lib.GABO_METRIC_AFFINE_INVARIANT, mode=_lib.GABO_OUT_GAUSSIAN):
-    """Gram matrix of the nested SPD kernels in two launches, no gradient (gabo_nested_spd_gram): x1 (..., N1, D_vec), x2 (..., N2, D_vec) Mandel
-    vectors of the ORIGINAL space, w (D, d_latent) with 2 <= d_latent <= 4 -> (..., N1, N2).  metric: _lib.GABO_METRIC_AFFINE_INVARIANT
-    (exp(-beta d_AI^2) of the projected points) or _lib.GABO_METRIC_LOG_EUCLIDEAN (exp(-beta ||logm - logm + 1e-15||_F^2))."""
+def _nested_spd_gram(entry, x1, x2, w, *scalars):
+    """The two nested Gram entries: the library's `entry` on dense sets (it takes no batch strides; `x2 is x1`: the set once, the same
+    address twice) and the projection matrix, `scalars` between the sizes and the workspace."""
     lib = _lib.load()
-    if x1.shape[:-2] != x2.shape[:-2] or x1.shape[-1] != x2.shape[-1]:
-        raise RuntimeError(f"batch/feature shapes differ: {tuple(x1.shape)} vs {tuple(x2.shape)} (no broadcasting, as in the reference)")
+    _check_two_sets(x1, x2, _NO_BROADCASTING)
     out_device = x1.device
     dev = _device_for(x1, x2, w)
-    same = x2 is x1
     a = _prep(x1, dev).contiguous()
-    b = a if same else _prep(x2, dev).contiguous()
+    b = a if x2 is x1 else _prep(x2, dev).contiguous()
     W = _prep(w, dev).contiguous()
     D = _mandel_dim(a.shape[-1])
     if W.dim() != 2 or W.shape[0] != D:
         raise RuntimeError(f"projection matrix must be ({D}, d_latent), got {tuple(W.shape)}")
     dl = int(W.shape[1])
     n1, n2 = a.shape[-2], b.shape[-2]
-    bshape = a.shape[:-2]
-    nb = 1
-    for k in bshape:
-        nb *= int(k)
-    out = torch.empty(bshape + (n1, n2), dtype=torch.float64, device=dev)
+    nb = math.prod(a.shape[:-2])
+    out = torch.empty(a.shape[:-2] + (n1, n2), dtype=torch.float64, device=dev)
     if out.numel() == 0:
         return _out(out, out_device)
     wsb = lib.gabo_nested_spd_gram_workspace_bytes(nb, n1, n2, dl)
-    ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
+    ws = _workspace(wsb, dev)
     status = _status_word(dev)
     with _on(dev):
-        rc = lib.gabo_nested_spd_gram(a.data_ptr(), b.data_ptr(), W.data_ptr(), out.data_ptr(), nb, n1, n2, D, dl, int(metric), float(beta), int(mode),
-                                      ws.data_ptr(), wsb, status.data_ptr(), _stream_ptr(dev))
-    _check_launch(rc, status, "gabo_nested_spd_gram")
+        rc = getattr(lib, entry)(a.data_ptr(), b.data_ptr(), W.data_ptr(), out.data_ptr(), nb, n1, n2, D, dl, *scalars, ws.data_ptr(), wsb,
+                                 status.data_ptr(), _stream_ptr(dev))
+    _check_launch(rc, status, entry)
     return _out(out, out_device)
+
+
+def nested_spd_gram(x1, x2, w, beta, metric=_lib.GABO_METRIC_AFFINE_INVARIANT, mode=_lib.GABO_OUT_GAUSSIAN):
+    """Gram matrix of the nested SPD kernels in two launches, no gradient (gabo_nested_spd_gram): x1 (..., N1, D_vec), x2 (..., N2, D_vec) Mandel
+    vectors of the ORIGINAL space, w (D, d_latent) with 2 <= d_latent <= 4 -> (..., N1, N2).  metric: _lib.GABO_METRIC_AFFINE_INVARIANT
+    (exp(-beta d_AI^2) of the projected points) or _lib.GABO_METRIC_LOG_EUCLIDEAN (exp(-beta ||logm - logm + 1e-15||_F^2))."""
+    return _nested_spd_gram("gabo_nested_spd_gram", x1, x2, w, int(metric), float(beta), int(mode))
 
 
 def nested_spd_matern_gram(x1, x2, w, lengthscale, nu):
     """Gram matrix of NestedSpdLogEuclideanMaternKernel in two launches, no gradient (gabo_nested_spd_matern_gram): shapes as nested_spd_gram;
     out = k_nu(||logm Y1 - logm Y2 + 1e-15||_F; lengthscale) of the projected points, nu in {0.5, 1.5, 2.5}, gpytorch's MaternKernel
     parametrisation.  With `x2 is x1` the set is projected once and the matrix is symmetric to the last bit."""
-    lib = _lib.load()
     nu2, lval = _matern_nu2(nu), _matern_lengthscale(lengthscale)
-    if x1.shape[:-2] != x2.shape[:-2] or x1.shape[-1] != x2.shape[-1]:
-        raise RuntimeError(f"batch/feature shapes differ: {tuple(x1.shape)} vs {tuple(x2.shape)} (no broadcasting, as in the reference)")
-    out_device = x1.device
-    dev = _device_for(x1, x2, w)
-    same = x2 is x1
-    a = _prep(x1, dev).contiguous()
-    b = a if same else _prep(x2, dev).contiguous()
-    W = _prep(w, dev).contiguous()
-    D = _mandel_dim(a.shape[-1])
-    if W.dim() != 2 or W.shape[0] != D:
-        raise RuntimeError(f"projection matrix must be ({D}, d_latent), got {tuple(W.shape)}")
-    dl = int(W.shape[1])
-    n1, n2 = a.shape[-2], b.shape[-2]
-    bshape = a.shape[:-2]
-    nb = 1
-    for k in bshape:
-        nb *= int(k)
-    out = torch.empty(bshape + (n1, n2), dtype=torch.float64, device=dev)
-    if out.numel() == 0:
-        return _out(out, out_device)
-    wsb = lib.gabo_nested_spd_gram_workspace_bytes(nb, n1, n2, dl)
-    ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
-    status = _status_word(dev)
-    with _on(dev):
-        rc = lib.gabo_nested_spd_matern_gram(a.data_ptr(), b.data_ptr(), W.data_ptr(), out.data_ptr(), nb, n1, n2, D, dl, lval, nu2, ws.data_ptr(), wsb,
-                                             status.data_ptr(), _stream_ptr(dev))
-    _check_launch(rc, status, "gabo_nested_spd_matern_gram")
-    return _out(out, out_device)
+    return _nested_spd_gram("gabo_nested_spd_matern_gram", x1, x2, w, lval, nu2)
 
 
 def nested_spd_gram_applicable(x1, x2, w, *params):
@@ -1136,9 +1121,7 @@ def nested_spd_gram_applicable(x1, x2, w, *params):
 
 def spd_logm_mandel(x_mandel):
     lib = _lib.load()
-    out_device = x_mandel.device
-    dev = _device_for(x_mandel)
-    x = _prep(x_mandel, dev).contiguous()
+    out_device, dev, x = _dense(x_mandel)
     d = _mandel_dim(x.shape[-1])
     out = torch.empty_like(x)
     with _on(dev):
@@ -1150,16 +1133,9 @@ def spd_logm_mandel(x_mandel):
 def frobenius_pairwise(x1, x2, beta=1.0, mode=_lib.GABO_OUT_GAUSSIAN):
     """Mandel vectors x1 (..., N1, d_vec), x2 (..., N2, d_vec) -> (..., N1, N2) Frobenius distance / kernel."""
     lib = _lib.load()
-    if x1.shape[:-2] != x2.shape[:-2] or x1.shape[-1] != x2.shape[-1]:
-        raise RuntimeError(f"batch/feature shapes differ: {tuple(x1.shape)} vs {tuple(x2.shape)}")
     out_device = x1.device
-    dev = _device_for(x1, x2)
-    a, b = _prep(x1, dev), _prep(x2, dev)
-    d = _mandel_dim(a.shape[-1])
-    n1, n2 = a.shape[-2], b.shape[-2]
-    a2, nb, s1 = _flatten_batch(a, 2)
-    b2, _, s2 = _flatten_batch(b, 2)
-    out = torch.empty(a.shape[:-2] + (n1, n2), dtype=torch.float64, device=dev)
+    dev, a2, b2, nb, n1, n2, s1, s2, out = _gram_sets(x1, x2)
+    d = _mandel_dim(a2.shape[-1])
     with _on(dev):
         _lib.check(lib.gabo_frobenius_pairwise(a2.data_ptr(), b2.data_ptr(), out.data_ptr(), nb, n1, n2, d, s1, s2, float(beta),
                                                int(mode), _stream_ptr(dev)), "gabo_frobenius_pairwise")
@@ -1169,9 +1145,7 @@ def frobenius_pairwise(x1, x2, beta=1.0, mode=_lib.GABO_OUT_GAUSSIAN):
 def spd_logm_mandel_backward(x_mandel, grad_y):
     """Gradient w.r.t. x (Mandel) of a loss whose gradient w.r.t. spd_logm_mandel(x) is grad_y."""
     lib = _lib.load()
-    out_device = x_mandel.device
-    dev = _device_for(x_mandel, grad_y)
-    x = _prep(x_mandel, dev).contiguous()
+    out_device, dev, x = _dense(x_mandel, grad_y)
     g = _prep(grad_y, dev).expand(x.shape).contiguous()
     d = _mandel_dim(x.shape[-1])
     out = torch.empty_like(x)
@@ -1205,27 +1179,18 @@ def frobenius_backward(x1, x2, grad_out, beta=1.0, mode=_lib.GABO_OUT_GAUSSIAN, 
     """Gradient of sum(grad_out * frobenius_pairwise(x1, x2)) with respect to x1 (wrt=1) or x2 (wrt=2)."""
     lib = _lib.load()
     out_device = (x1 if wrt == 1 else x2).device
-    dev = _device_for(x1, x2, grad_out)
-    a, b, g = _prep(x1, dev), _prep(x2, dev), _prep(grad_out, dev).contiguous()
-    d = _mandel_dim(a.shape[-1])
-    n1, n2 = a.shape[-2], b.shape[-2]
-    bshape = a.shape[:-2]
-    a2, nb, s1 = _flatten_batch(a, 2)
-    b2, _, s2 = _flatten_batch(b, 2)
-    if wrt == 1:
-        first, second, m1, m2, sf, ss, go_si, go_sj, sgn = a2, b2, n1, n2, s1, s2, n2, 1, 1.0
-    else:
-        first, second, m1, m2, sf, ss, go_si, go_sj, sgn = b2, a2, n2, n1, s2, s1, 1, n2, -1.0
-    gx = torch.zeros(bshape + (m1, a.shape[-1]), dtype=torch.float64, device=dev)
+    dev, a2, b2, nb, n1, n2, s1, s2, bshape = _two_sets(x1, x2, (grad_out,))
+    g = _prep(grad_out, dev).contiguous()
+    d = _mandel_dim(a2.shape[-1])
+    first, second, m1, m2, sf, ss, go_si, go_sj, sgn = _wrt_roles(wrt, a2, b2, n1, n2, s1, s2, n2, 1)
+    gx = torch.zeros(bshape + (m1, a2.shape[-1]), dtype=torch.float64, device=dev)
     if gx.numel() == 0 or m2 == 0:
         return _out(gx, out_device)
     with _on(dev):
         _lib.check(lib.gabo_frobenius_backward(first.data_ptr(), second.data_ptr(), g.data_ptr(), gx.data_ptr(), nb, m1, m2, d, sf,
                                                ss, n1 * n2, go_si, go_sj, float(beta), int(mode), sgn, _stream_ptr(dev)),
                    "gabo_frobenius_backward")
-    if sf == 0 and nb > 1:
-        gx = gx.reshape(nb, m1, -1).sum(0).expand(bshape + (m1, a.shape[-1]))
-    return _out(gx, out_device)
+    return _out(_sum_shared_first_set(gx, nb, sf), out_device)
 
 
 class _FrobeniusKernelFunction(torch.autograd.Function):
@@ -1237,8 +1202,7 @@ class _FrobeniusKernelFunction(torch.autograd.Function):
         out = frobenius_pairwise(x1, x2, bval, mode)
         ctx.save_for_backward(x1, x2, out)
         ctx.bval, ctx.mode = bval, mode
-        ctx.beta_shape = beta.shape if torch.is_tensor(beta) else None
-        ctx.beta_device = beta.device if torch.is_tensor(beta) else None
+        _note_param(ctx, beta)
         return out
 
     @staticmethod
@@ -1257,19 +1221,13 @@ class _FrobeniusKernelFunction(torch.autograd.Function):
                 dist = frobenius_pairwise(x1, x2, 1.0, _lib.GABO_OUT_DISTANCE).to(out.device)
                 t = dist * dist if ctx.mode == _lib.GABO_OUT_GAUSSIAN else dist
                 gb = -(grad_out * out * t).sum()
-            gb = gb.reshape(ctx.beta_shape).to(ctx.beta_device)
+            gb = _param_grad(ctx, gb)
         return g1, g2, gb, None
 
 
 def frobenius_kernel(x1, x2, beta, mode=_lib.GABO_OUT_GAUSSIAN):
     """Differentiable entry point used by SpdFrobeniusGaussianKernel / SpdLogEuclideanGaussianKernel."""
-    if torch.is_tensor(beta):
-        if beta.numel() != 1:
-            raise RuntimeError("gabotorch_amd SPD kernels take a single lengthscale (batch_shape == ())")
-        beta = beta.double()
-    else:
-        beta = torch.tensor(float(beta), dtype=torch.float64)
-    return _FrobeniusKernelFunction.apply(x1, x2, beta, int(mode))
+    return _FrobeniusKernelFunction.apply(x1, x2, _scalar_param(beta, _ONE_SPD_LENGTHSCALE), int(mode))
 
 
 # ---- Matern kernels on the flat SPD metrics (csrc/flat_matern.hip): features are Mandel vectors, the distance is frobenius_pairwise's ----
@@ -1286,9 +1244,8 @@ def _matern_nu2(nu):
 
 def _matern_lengthscale(lengthscale):
     """the lengthscale as a positive finite Python float (ValueError otherwise), as the C entries check it"""
-    import math
     if torch.is_tensor(lengthscale) and lengthscale.numel() != 1:
-        raise RuntimeError("gabotorch_amd SPD kernels take a single lengthscale (batch_shape == ())")
+        raise RuntimeError(_ONE_SPD_LENGTHSCALE)
     value = float(lengthscale)
     if not (value > 0.0 and math.isfinite(value)):
         raise ValueError(f"the lengthscale must be positive and finite, got {value!r}")
@@ -1301,16 +1258,10 @@ def flat_matern_pairwise(x1, x2, lengthscale, nu):
     `x2 is x1` the matrix is symmetric to the last bit."""
     lib = _lib.load()
     nu2, lval = _matern_nu2(nu), _matern_lengthscale(lengthscale)
-    if x1.shape[:-2] != x2.shape[:-2] or x1.shape[-1] != x2.shape[-1]:
-        raise RuntimeError(f"batch/feature shapes differ: {tuple(x1.shape)} vs {tuple(x2.shape)}")
     out_device = x1.device
-    dev = _device_for(x1, x2)
-    a, b = _prep(x1, dev), _prep(x2, dev)
-    d = _mandel_dim(a.shape[-1])
-    n1, n2 = a.shape[-2], b.shape[-2]
-    a2, nb, s1 = _flatten_batch(a, 2)
-    b2, _, s2 = (a2, nb, s1) if x2 is x1 else _flatten_batch(b, 2)      # (one point set: the same pointer, and with it an exactly symmetric matrix)
-    out = torch.empty(a.shape[:-2] + (n1, n2), dtype=torch.float64, device=dev)
+    # (one point set: the same pointer, and with it an exactly symmetric matrix)
+    dev, a2, b2, nb, n1, n2, s1, s2, out = _gram_sets(x1, x2, one_set=x2 is x1)
+    d = _mandel_dim(a2.shape[-1])
     with _on(dev):
         _lib.check(lib.gabo_flat_matern_pairwise(a2.data_ptr(), b2.data_ptr(), out.data_ptr(), nb, n1, n2, d, s1, s2, lval, nu2,
                                                  _stream_ptr(dev)), "gabo_flat_matern_pairwise")
@@ -1324,31 +1275,22 @@ def flat_matern_backward(x1, x2, grad_out, lengthscale, nu, wrt=1):
     if wrt not in (1, 2):
         raise ValueError(f"wrt must be 1 or 2, got {wrt!r}")
     out_device = (x1 if wrt == 1 else x2).device
-    dev = _device_for(x1, x2, grad_out)
-    a, b, g = _prep(x1, dev), _prep(x2, dev), _prep(grad_out, dev)
-    d = _mandel_dim(a.shape[-1])
-    n1, n2 = a.shape[-2], b.shape[-2]
-    bshape = a.shape[:-2]
-    a2, nb, s1 = _flatten_batch(a, 2)
-    b2, _, s2 = _flatten_batch(b, 2)
+    dev, a2, b2, nb, n1, n2, s1, s2, bshape = _two_sets(x1, x2, (grad_out,))
+    g = _prep(grad_out, dev)
+    d = _mandel_dim(a2.shape[-1])
     if g.dim() == 2 and tuple(g.shape) == (n1, n2) and nb == 1 and min(g.stride()) >= 0:
         go_b, go_i, go_j = 0, g.stride(0), g.stride(1)          # (a strided matrix - a transpose, a slice - is read in place)
     else:
         g = g.expand(bshape + (n1, n2)).contiguous()
         go_b, go_i, go_j = n1 * n2, n2, 1
-    if wrt == 1:
-        first, second, m1, m2, sf, ss, sgn = a2, b2, n1, n2, s1, s2, 1.0
-    else:
-        first, second, m1, m2, sf, ss, go_i, go_j, sgn = b2, a2, n2, n1, s2, s1, go_j, go_i, -1.0
-    gx = torch.zeros(bshape + (m1, a.shape[-1]), dtype=torch.float64, device=dev)
+    first, second, m1, m2, sf, ss, go_i, go_j, sgn = _wrt_roles(wrt, a2, b2, n1, n2, s1, s2, go_i, go_j)
+    gx = torch.zeros(bshape + (m1, a2.shape[-1]), dtype=torch.float64, device=dev)
     if gx.numel() == 0 or m2 == 0:
         return _out(gx, out_device)
     with _on(dev):
         _lib.check(lib.gabo_flat_matern_backward(first.data_ptr(), second.data_ptr(), g.data_ptr(), gx.data_ptr(), nb, m1, m2, d, sf, ss,
                                                  go_b, go_i, go_j, lval, nu2, sgn, _stream_ptr(dev)), "gabo_flat_matern_backward")
-    if sf == 0 and nb > 1:
-        gx = gx.reshape(nb, m1, -1).sum(0).expand(bshape + (m1, a.shape[-1]))
-    return _out(gx, out_device)
+    return _out(_sum_shared_first_set(gx, nb, sf), out_device)
 
 
 def flat_matern_from_distance(r, lengthscale, nu, order=0):
@@ -1357,9 +1299,7 @@ def flat_matern_from_distance(r, lengthscale, nu, order=0):
     nu2, lval = _matern_nu2(nu), _matern_lengthscale(lengthscale)
     if order not in (0, 1):
         raise ValueError(f"order must be 0 or 1, got {order!r}")
-    out_device = r.device
-    dev = _device_for(r)
-    c = _prep(r, dev).contiguous()
+    out_device, dev, c = _dense(r)
     out = torch.empty_like(c)
     with _on(dev):
         _lib.check(lib.gabo_flat_matern_from_distance(c.data_ptr(), out.data_ptr(), c.numel(), lval, nu2, int(order), _stream_ptr(dev)),
@@ -1376,8 +1316,7 @@ class _FlatMaternKernelFunction(torch.autograd.Function):
         out = flat_matern_pairwise(x1, x1 if same else x2, lval, nu)
         ctx.save_for_backward(x1, x2)
         ctx.lval, ctx.nu = lval, nu
-        ctx.ls_shape = lengthscale.shape if torch.is_tensor(lengthscale) else None
-        ctx.ls_device = lengthscale.device if torch.is_tensor(lengthscale) else None
+        _note_param(ctx, lengthscale)
         return out
 
     @staticmethod
@@ -1391,20 +1330,14 @@ class _FlatMaternKernelFunction(torch.autograd.Function):
             g2 = flat_matern_backward(x1, x2, grad_out, ctx.lval, ctx.nu, wrt=2).to(x2.dtype)
         if ctx.needs_input_grad[2]:      # sum_ij g_ij dk_ij/dl: the distance launch, then the element-wise one
             dist = frobenius_pairwise(x1, x2, 1.0, _lib.GABO_OUT_DISTANCE).to(grad_out.device)
-            gl = (grad_out * flat_matern_from_distance(dist, ctx.lval, ctx.nu, order=1)).sum().reshape(ctx.ls_shape).to(ctx.ls_device)
+            gl = _param_grad(ctx, (grad_out * flat_matern_from_distance(dist, ctx.lval, ctx.nu, order=1)).sum())
         return g1, g2, gl, None, None
 
 
 def flat_matern_kernel(x1, x2, lengthscale, nu):
     """Differentiable entry point used by SpdFrobeniusMaternKernel / SpdLogEuclideanMaternKernel (first order in x1, x2 and the lengthscale)."""
     _matern_nu2(nu)
-    if torch.is_tensor(lengthscale):
-        if lengthscale.numel() != 1:
-            raise RuntimeError("gabotorch_amd SPD kernels take a single lengthscale (batch_shape == ())")
-        lengthscale = lengthscale.double()
-    else:
-        lengthscale = torch.tensor(float(lengthscale), dtype=torch.float64)
-    return _FlatMaternKernelFunction.apply(x1, x2, lengthscale, float(nu), x2 is x1)
+    return _FlatMaternKernelFunction.apply(x1, x2, _scalar_param(lengthscale, _ONE_SPD_LENGTHSCALE), float(nu), x2 is x1)
 
 
 # ---- Matern / heat kernels of the affine-invariant SPD metric by random phase features (csrc/spd_ai_spectral.hip) ----
@@ -1414,7 +1347,6 @@ def flat_matern_kernel(x1, x2, lengthscale, nu):
 
 def _spectral_nu(nu):
     """nu as a float: positive, or math.inf for the heat kernel (ValueError otherwise)"""
-    import math
     if isinstance(nu, bool) or not isinstance(nu, (int, float)) or not (nu > 0.0) or math.isnan(nu):
         raise ValueError(f"nu must be a positive number or math.inf, got {nu!r}")
     return float(nu)
@@ -1431,7 +1363,6 @@ def spd_ai_spectral_base(dim, num_features, nu, seed):
       2. Generator.permuted(e, axis=1): the d entries of every row in random order;
       3. finite nu only: gamma(shape nu, scale 1, L);
       4. standard_normal((L, d, d)) = Q R;  H = Q with its columns multiplied by sign(diag R): Haar on O(d)."""
-    import math
     import numpy as np
     nu = _spectral_nu(nu)
     if not (isinstance(dim, int) and dim >= 2) or not (isinstance(num_features, int) and num_features >= 1):
@@ -1448,12 +1379,8 @@ def spd_ai_spectral_points(base, lengthscale, nu):
     """(e, gamma, H) and a lengthscale kappa -> (lam (L, d), w (L,)), torch fp64 on the lengthscale's device, differentiable in the lengthscale:
     lam = e / kappa (nu = inf) or e sqrt((nu / kappa^2 + |rho|^2 / 2) / gamma), |rho|^2 = d (d^2 - 1) / 48;
     w = prod_{i<j} tanh(pi |lam_i - lam_j|) in (0, 1], the part of the Plancherel density the draw of e leaves out (an importance weight)."""
-    import math
     nu = _spectral_nu(nu)
-    ls = lengthscale if torch.is_tensor(lengthscale) else torch.tensor(float(lengthscale), dtype=torch.float64)
-    if ls.numel() != 1:
-        raise RuntimeError("gabotorch_amd SPD kernels take a single lengthscale (batch_shape == ())")
-    ls = ls.double().reshape(())
+    ls = _scalar_param(lengthscale, _ONE_SPD_LENGTHSCALE).reshape(())
     e, gamma = (torch.as_tensor(t, dtype=torch.float64, device=ls.device) if t is not None else None for t in base[:2])
     d = e.shape[-1]
     if math.isinf(nu):
@@ -1583,9 +1510,8 @@ def gp_acquisition(kstar, alpha, linv, linv_t, mean, outputscale, kxx, best_f, k
     r, n = ks.shape
     value = torch.empty(r, dtype=torch.float64, device=dev)
     grad = torch.empty_like(ks) if need_grad else None
-    ptr = lambda t_: None if t_ is None else t_.data_ptr()   # noqa: E731
     with _on(dev):
-        _lib.check(lib.gabo_gp_acquisition(ks.data_ptr(), alpha.data_ptr(), ptr(linv), ptr(linv_t), value.data_ptr(), ptr(grad), r, n,
+        _lib.check(lib.gabo_gp_acquisition(ks.data_ptr(), alpha.data_ptr(), _ptr(linv), _ptr(linv_t), value.data_ptr(), _ptr(grad), r, n,
                                            float(mean), float(outputscale), float(kxx), float(best_f), int(kind), 1 if maximize else 0,
                                            float(out_sign), _stream_ptr(dev)), "gabo_gp_acquisition")
     return value, grad
@@ -1684,9 +1610,29 @@ def _gp_mll_large(e, y, theta, outputscale, noise, mean, gram, want_w):
     w = torch.empty(n, n, dtype=torch.float64, device=dev) if want_w else None
     with _on(dev):
         _lib.check(lib.gabo_gp_mll_large(e.data_ptr(), y.data_ptr(), n, float(theta), float(outputscale), float(noise), float(mean),
-                                         1 if gram else 0, out.data_ptr(), None if w is None else w.data_ptr(), ws.data_ptr(),
+                                         1 if gram else 0, out.data_ptr(), _ptr(w), ws.data_ptr(),
                                          ws.numel() * 8, _stream_ptr(dev)), "gabo_gp_mll_large")
     return out, w
+
+
+_mll_host_out = {}
+
+
+def _mll_host(dev):
+    """The page-locked result buffer of the small likelihood launches, one per device, which the kernel addresses itself: -> (tensor, its
+    numpy view).  An L-BFGS evaluation is the launch and a stream wait - no device buffer, no copy back (a surrogate fit is ~35 of these;
+    worth 4 % of it: 1.57 -> 1.51 ms on 5 ... 20 observations - the rest is scipy's L-BFGS-B and the Python chain rule around the launch)."""
+    ent = _mll_host_out.get(dev.index)
+    if ent is None:
+        host = _pinned(8).zero_()
+        ent = _mll_host_out[dev.index] = (host, host.numpy())
+    return ent
+
+
+def _mll_wait_and_read(dev, host_np):
+    """after the launch that was handed _mll_host's buffer: the six results as Python floats"""
+    torch.cuda.current_stream(dev).synchronize()
+    return host_np[:6].tolist()
 
 
 def gp_mll(e, y, theta, outputscale, noise, mean):
@@ -1700,23 +1646,15 @@ def gp_mll(e, y, theta, outputscale, noise, mean):
         raise RuntimeError("gp_mll: e must be a contiguous n x n matrix and y a contiguous vector of n targets")
     if n > _lib.GABO_GP_MLL_MAX_N:
         return _gp_mll_large(e, y, theta, outputscale, noise, mean, False, False)[0].tolist()
-    # the six results go straight into page-locked host memory the kernel addresses itself (one buffer per device): an L-BFGS evaluation is the launch
-    # and a stream wait - no device buffer, no copy back (a surrogate fit is ~35 of these; worth 4 % of it: 1.57 -> 1.51 ms on 5 ... 20
-    # observations - the rest is scipy's L-BFGS-B and the Python chain rule around the launch)
-    ent = _mll_host_out.get(dev.index)
-    if ent is None:
-        host = torch.zeros(8, dtype=torch.float64).pin_memory()
-        ent = _mll_host_out[dev.index] = (host, host.numpy())
-    host, host_np = ent
+    # (the inner loop of a fit: _mll_host only when this device has no buffer yet, and _mll_wait_and_read written out - the two calls measured
+    # 0.1 us on the 22.8 us of an evaluation at n = 20)
+    host, host_np = _mll_host_out.get(dev.index) or _mll_host(dev)
     with _on(dev):
         stream = _stream_ptr(dev)
         _lib.check(lib.gabo_gp_mll(e.data_ptr(), y.data_ptr(), n, float(theta), float(outputscale), float(noise), float(mean),
                                    host.data_ptr(), stream), "gabo_gp_mll")
         torch.cuda.current_stream(dev).synchronize()
     return host_np[:6].tolist()
-
-
-_mll_host_out = {}
 
 
 def gp_mll_gram(k, y, outputscale, noise, mean, want_w=True):
@@ -1734,8 +1672,8 @@ def gp_mll_gram(k, y, outputscale, noise, mean, want_w=True):
     out = torch.empty(6, dtype=torch.float64, device=dev)
     w = torch.empty(n, n, dtype=torch.float64, device=dev) if want_w else None
     with _on(dev):
-        _lib.check(lib.gabo_gp_mll_gram(k.data_ptr(), y.data_ptr(), n, float(outputscale), float(noise), float(mean), out.data_ptr(),
-                                        None if w is None else w.data_ptr(), _stream_ptr(dev)), "gabo_gp_mll_gram")
+        _lib.check(lib.gabo_gp_mll_gram(k.data_ptr(), y.data_ptr(), n, float(outputscale), float(noise), float(mean), out.data_ptr(), _ptr(w),
+                                        _stream_ptr(dev)), "gabo_gp_mll_gram")
     return out, w
 
 
@@ -1760,17 +1698,12 @@ def gp_mll_series(c, y, coeff, dcoeff, series_dim, outputscale, noise, mean):
             d_kappa = (0.5 * float(outputscale)) * (w * sphere_zonal_from_inner(c, da, series_dim)).sum()
             out[1] = torch.where(out[5] == 0, d_kappa, torch.zeros_like(d_kappa))
         return out.tolist()
-    ent = _mll_host_out.get(dev.index)             # (the page-locked result buffer of gp_mll: one launch, one stream wait)
-    if ent is None:
-        host = torch.zeros(8, dtype=torch.float64).pin_memory()
-        ent = _mll_host_out[dev.index] = (host, host.numpy())
-    host, host_np = ent
+    host, host_np = _mll_host(dev)                 # (as gp_mll: one launch, one stream wait)
     with _on(dev):
         stream = _stream_ptr(dev)
         _lib.check(lib.gabo_gp_mll_series(c.data_ptr(), y.data_ptr(), n, ptr, dptr, na, int(series_dim), float(outputscale), float(noise),
                                           float(mean), host.data_ptr(), stream), "gabo_gp_mll_series")
-        torch.cuda.current_stream(dev).synchronize()
-    return host_np[:6].tolist()
+        return _mll_wait_and_read(dev, host_np)
 
 
 def gp_mll_matern(r, y, lengthscale, nu, outputscale, noise, mean):
@@ -1790,17 +1723,12 @@ def gp_mll_matern(r, y, lengthscale, nu, outputscale, noise, mean):
         d_l = (0.5 * float(outputscale)) * (w * flat_matern_from_distance(r, lval, nu, 1)).sum()
         out[1] = torch.where(out[5] == 0, d_l, torch.zeros_like(d_l))
         return out.tolist()
-    ent = _mll_host_out.get(dev.index)             # (the page-locked result buffer of gp_mll: one launch, one stream wait)
-    if ent is None:
-        host = torch.zeros(8, dtype=torch.float64).pin_memory()
-        ent = _mll_host_out[dev.index] = (host, host.numpy())
-    host, host_np = ent
+    host, host_np = _mll_host(dev)                 # (as gp_mll: one launch, one stream wait)
     with _on(dev):
         stream = _stream_ptr(dev)
         _lib.check(lib.gabo_gp_mll_matern(r.data_ptr(), y.data_ptr(), n, lval, nu2, float(outputscale), float(noise), float(mean),
                                           host.data_ptr(), stream), "gabo_gp_mll_matern")
-        torch.cuda.current_stream(dev).synchronize()
-    return host_np[:6].tolist()
+        return _mll_wait_and_read(dev, host_np)
 
 
 def gram_extreme_eigenvalues(e, thetas):
@@ -1822,18 +1750,16 @@ def gram_extreme_eigenvalues(e, thetas):
         raise ValueError(f"gram_extreme_eigenvalues: thetas must be (P,) with P >= 1, got {tuple(th.shape)}")
     th = th.to(device=dev, dtype=torch.float64).contiguous()
     bshape, nt = tuple(e.shape[:-2]), th.numel()
-    nb = 1
-    for s in bshape:
-        nb *= s
+    nb = math.prod(bshape)
     if nb < 1:
         raise ValueError(f"gram_extreme_eigenvalues: empty batch {tuple(e.shape)}")
     ec = e.contiguous()
     out = torch.empty(bshape + (nt, 2), dtype=torch.float64, device=dev)
     wsb = int(lib.gabo_gram_extreme_eig_workspace_bytes(nb, n, nt))
-    ws = torch.empty(wsb // 8, dtype=torch.float64, device=dev) if wsb else None
+    ws = _workspace(wsb, dev) if wsb else None
     with _on(dev):
-        _lib.check(lib.gabo_gram_extreme_eig(ec.data_ptr(), nb, n, th.data_ptr(), nt, out.data_ptr(), None if ws is None else ws.data_ptr(),
-                                             wsb, _stream_ptr(dev)), "gabo_gram_extreme_eig")
+        _lib.check(lib.gabo_gram_extreme_eig(ec.data_ptr(), nb, n, th.data_ptr(), nt, out.data_ptr(), _ptr(ws), wsb, _stream_ptr(dev)),
+                   "gabo_gram_extreme_eig")
     return out
 
 
@@ -1861,7 +1787,7 @@ def gp_posterior_joint(kstar, kss, linv, alpha, mean, outputscale, inplace=True)
     _require(dev, kstar=ks, kss=cov, linv=li, alpha=al)
     out = torch.empty(2, m, dtype=torch.float64, device=dev)
     wsb = int(lib.gabo_gp_posterior_joint_workspace_bytes(m, n))
-    ws = torch.empty(wsb // 8, dtype=torch.float64, device=dev)
+    ws = _workspace(wsb, dev)
     with _on(dev):
         _lib.check(lib.gabo_gp_posterior_joint(ks.data_ptr(), cov.data_ptr(), li.data_ptr(), al.data_ptr(), m, n, float(mean), float(outputscale),
                                                out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), wsb, _stream_ptr(dev)),
@@ -1919,11 +1845,10 @@ def gp_condition(linv, alpha, kcross, knew, y_new=None, outputscale=1.0, noise=1
         cuts.append(cuts[-1] + p)
     linv_o, linv_t_o, kinv_o, alpha_o, y_used, ws = (flat[a:b] if b > a else None for a, b in zip(cuts[:-1], cuts[1:]))
     linv_o, linv_t_o, kinv_o = (None if v is None else v.view(m, m) for v in (linv_o, linv_t_o, kinv_o))
-    ptr = lambda t_: None if t_ is None else t_.data_ptr()   # noqa: E731
     status = _status_word(dev, force=True)
     with _on(dev):
-        rc = lib.gabo_gp_condition(li.data_ptr(), al.data_ptr(), ptr(ki), n, kc.data_ptr(), kn.data_ptr(), ptr(yn), t, float(outputscale),
-                                   float(noise), float(mean), linv_o.data_ptr(), ptr(linv_t_o), alpha_o.data_ptr(), ptr(kinv_o),
+        rc = lib.gabo_gp_condition(li.data_ptr(), al.data_ptr(), _ptr(ki), n, kc.data_ptr(), kn.data_ptr(), _ptr(yn), t, float(outputscale),
+                                   float(noise), float(mean), linv_o.data_ptr(), _ptr(linv_t_o), alpha_o.data_ptr(), _ptr(kinv_o),
                                    y_used.data_ptr(), ws.data_ptr(), wsb, status.data_ptr(), _stream_ptr(dev))
     _lib.check(rc, "gabo_gp_condition")
     # (read back whatever set_error_checking says, at the caller's next synchronisation point: as gp_factor(defer_check=True))
@@ -1972,9 +1897,7 @@ def mvn_sample(mean, cov, sample_shape=(), seed=None, base_samples=None, return_
     if m < 1:
         raise ValueError("mvn_sample: empty covariance")
     shape = tuple(int(s) for s in sample_shape)
-    count = 1
-    for s in shape:
-        count *= s
+    count = math.prod(shape)
     mu = _prep(torch.as_tensor(mean), dev).reshape(-1).contiguous()
     if mu.numel() != m:
         raise ValueError(f"mvn_sample: mean has {mu.numel()} entries, cov is {m} x {m}")
@@ -2002,7 +1925,7 @@ def mvn_sample(mean, cov, sample_shape=(), seed=None, base_samples=None, return_
     status = torch.zeros(2, dtype=torch.int32, device=dev)       # (a word of its own: status[1], the rung, outlives the error check)
     with _on(dev):
         _lib.check(lib.gabo_mvn_sample(mu.data_ptr(), cv.data_ptr(), m, count, _mvn_seed(seed) if z is None else 0,
-                                       None if z is None else z.data_ptr(), out.data_ptr(), None if tril is None else tril.data_ptr(),
+                                       _ptr(z), out.data_ptr(), _ptr(tril),
                                        status.data_ptr(), _stream_ptr(dev)), "gabo_mvn_sample")
     _raise_if_not_spd(status, "gabo_mvn_sample", message=_MVN_MESSAGE)
     out = out.reshape(shape + (m,))
@@ -2066,9 +1989,7 @@ def spd_sample(n, d, min_eig, max_eig, seed, device, mandel=False, first=0):
 def nested_sphere_epilogue(rotated, dist_to_axis, mode=0):
     """Per-point part of the nested-sphere projection on already rotated points (..., d) -> (..., d-1) [mode 0] / (..., d) [mode 1]."""
     lib = _lib.load()
-    out_device = rotated.device
-    dev = _device_for(rotated)
-    u = _prep(rotated, dev).contiguous()
+    out_device, dev, u = _dense(rotated)
     d = u.shape[-1]
     n = u.numel() // d
     out = torch.empty(u.shape[:-1] + ((d - 1) if mode == 0 else d,), dtype=torch.float64, device=dev)
@@ -2080,9 +2001,7 @@ def nested_sphere_epilogue(rotated, dist_to_axis, mode=0):
 
 def nested_sphere_epilogue_backward(rotated, grad_out, dist_to_axis):
     lib = _lib.load()
-    out_device = rotated.device
-    dev = _device_for(rotated, grad_out)
-    u = _prep(rotated, dev).contiguous()
+    out_device, dev, u = _dense(rotated, grad_out)
     g = _prep(grad_out, dev).contiguous()
     d = u.shape[-1]
     gu = torch.empty_like(u)
@@ -2205,8 +2124,7 @@ class NestedSphereReconstruction:
         ent = self._buffers.get(P)
         if ent is None:
             ws = max(int(lib.gabo_nested_sphere_reconstruction_workspace_bytes(P, max(self.N, 1), self.D, self.L)), 16)
-            ent = self._buffers[P] = dict(hin=torch.empty(P * self.L, dtype=torch.float64).pin_memory(),
-                                          hout=torch.empty(P * (1 + self.L), dtype=torch.float64).pin_memory(),
+            ent = self._buffers[P] = dict(hin=_pinned(P * self.L), hout=_pinned(P * (1 + self.L)),
                                           din=torch.empty(P * self.L, dtype=torch.float64, device=self.device),
                                           dout=torch.empty(P * (1 + self.L), dtype=torch.float64, device=self.device),
                                           ws=torch.empty(ws, dtype=torch.uint8, device=self.device))
@@ -2459,10 +2377,9 @@ def sphere_constraints_eval(x, kinds, indices, bounds, centres=None, want_grad=T
     ci = (ctypes.c_int * max(nc, 1))(*indices)
     cb = (ctypes.c_double * max(nc, 1))(*bounds)
     with _on(dev):
-        _lib.check(lib.gabo_sphere_constraints_eval(xx.data_ptr(), r, dim, nc, ck, ci, cb, None if centres is None else centres.data_ptr(),
-                                                    0 if centres is None else int(centres.shape[0]), values.data_ptr(),
-                                                    None if grads is None else grads.data_ptr(), _stream_ptr(dev)),
-                   "gabo_sphere_constraints_eval")
+        _lib.check(lib.gabo_sphere_constraints_eval(xx.data_ptr(), r, dim, nc, ck, ci, cb, _ptr(centres),
+                                                    0 if centres is None else int(centres.shape[0]), values.data_ptr(), _ptr(grads),
+                                                    _stream_ptr(dev)), "gabo_sphere_constraints_eval")
     return (values, grads) if want_grad else values
 
 
@@ -2501,8 +2418,8 @@ def sphere_sample(count, dim, seed, constraints=None, device=None):
     cb = (ctypes.c_double * max(nc, 1))(*bounds)
     with _on(dev):
         _lib.check(lib.gabo_sphere_sample(out.data_ptr(), count, dim, int(seed) & 0xFFFFFFFFFFFFFFFF, nc, 0, ck, ci, cb,
-                                          None if centres is None else centres.data_ptr(), 0 if centres is None else int(centres.shape[0]),
-                                          flag.data_ptr(), _stream_ptr(dev)), "gabo_sphere_sample")
+                                          _ptr(centres), 0 if centres is None else int(centres.shape[0]), flag.data_ptr(), _stream_ptr(dev)),
+                   "gabo_sphere_sample")
     return out, bool(flag.item())
 
 
@@ -2518,9 +2435,8 @@ def sphere_manifold_op(op, x, u, v=None, w=None):
     dim = shape[-1]
     n = X.numel() // dim
     out = torch.empty(shape[:-1] if op == _lib.GABO_SPH_DIST else shape, dtype=torch.float64, device=dev)
-    ptr = lambda t_: None if t_ is None else t_.data_ptr()   # noqa: E731
     with _on(dev):
-        _lib.check(lib.gabo_sphere_manifold_op(int(op), ptr(X), ptr(U), ptr(V), ptr(W), out.data_ptr(), n, dim, _stream_ptr(dev)),
+        _lib.check(lib.gabo_sphere_manifold_op(int(op), _ptr(X), _ptr(U), _ptr(V), _ptr(W), out.data_ptr(), n, dim, _stream_ptr(dev)),
                    "gabo_sphere_manifold_op")
     return _out(out, out_device)
 
@@ -2626,11 +2542,10 @@ def spd_frechet_mean(x_mandel, weights=None, iters=10, start=None, return_residu
         mean = torch.empty(nb, xs.shape[-1], dtype=torch.float64, device=dev)
         resid = torch.empty(nb, iters, dtype=torch.float64, device=dev) if return_residual else None
         wsb = lib.gabo_spd_frechet_mean_workspace_bytes(nb, n, d)
-        ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
+        ws = _workspace(wsb, dev)
         status = _status_word(dev)
-        ptr = lambda t_: None if t_ is None else t_.data_ptr()   # noqa: E731
         with _on(dev):
-            rc = lib.gabo_spd_frechet_mean(xs.data_ptr(), ptr(w), ptr(s), mean.data_ptr(), ptr(resid), nb, n, d, iters, ws.data_ptr(), wsb,
+            rc = lib.gabo_spd_frechet_mean(xs.data_ptr(), _ptr(w), _ptr(s), mean.data_ptr(), _ptr(resid), nb, n, d, iters, ws.data_ptr(), wsb,
                                            status.data_ptr(), _stream_ptr(dev))
         _lib.check(rc, "gabo_spd_frechet_mean")
         _raise_if_not_spd(status, "gabo_spd_frechet_mean", message=_spd_mean_message(nb, n))
@@ -2638,7 +2553,6 @@ def spd_frechet_mean(x_mandel, weights=None, iters=10, start=None, return_residu
     if return_residual:
         return _out(mean, out_device), resid.reshape(bshape + (iters,)).to(out_device)
     return _out(mean, out_device)
-
 
 
 def sphere_karcher_mean(x, weights=None, iters=10, start=None, return_residual=False):
@@ -2657,10 +2571,9 @@ def sphere_karcher_mean(x, weights=None, iters=10, start=None, return_residual=F
     resid = torch.empty(nb, iters, dtype=torch.float64, device=dev) if return_residual else None
     if nb > 0:
         wsb = lib.gabo_sphere_karcher_mean_workspace_bytes(nb, n, dim)
-        ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=dev)
-        ptr = lambda t_: None if t_ is None else t_.data_ptr()   # noqa: E731
+        ws = _workspace(wsb, dev)
         with _on(dev):
-            rc = lib.gabo_sphere_karcher_mean(xs.data_ptr(), ptr(w), ptr(s), mean.data_ptr(), ptr(resid), nb, n, dim, iters, ws.data_ptr(), wsb,
+            rc = lib.gabo_sphere_karcher_mean(xs.data_ptr(), _ptr(w), _ptr(s), mean.data_ptr(), _ptr(resid), nb, n, dim, iters, ws.data_ptr(), wsb,
                                               _stream_ptr(dev))
         _lib.check(rc, "gabo_sphere_karcher_mean")
     mean = mean.reshape(bshape + (dim,))
