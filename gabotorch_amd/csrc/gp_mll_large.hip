@@ -10,11 +10,18 @@
 //     P <- -P^-1,   B <- B P^-1 (every other block row),   C <- C - B P^-1 B^T (every other pair of block rows),
 // and sweeping the blocks of Ky one after the other leaves -Ky^-1 in the matrix part, alpha = Ky^-1 r in the border and -r.alpha in the corner;
 // det Ky is the product of the determinants of the pivot blocks as they are met (Schur complements: positive definite iff Ky is).
+// P^-1 is never applied as a matrix: with P = L L^T every product through it is taken in the factored form,
+//     B P^-1 B^T = (B L^-T)(B L^-T)^T,   B P^-1 = (B L^-T) L^-1,   P^-1 = L^-T L^-1.
+// A pivot block that holds fresh training points next to near-duplicates of earlier ones has pivots from 1 down to the noise: its own condition
+// number reaches 1e6, and a product through the explicit inverse has terms that much larger than its result - an error ON TOP of cond(Ky):
+// measured on cond(Ky) = 3e8 as 8 cond(Ky) 2^-53 in W against 0.1 cond(Ky) 2^-53 for the scalar sweeps of gp_mll.hip
+// (tests/test_gpu_gp_ill_conditioned.py).  The factored products have no such terms, and, being the same sums for tile (i, j) and tile (j, i),
+// keep both triangles equal bit for bit.
 // One step is ONE launch, embarrassingly parallel over tiles (mll_step_kernel: one block per tile (i, j)):
-//   the sweep on pivot block k:   M_ij -= G_i H_j^T,  M_ik <- G_i,  M_kj <- G_j^T,  M_kk <- -P^-1   with the panel G_i = M_ik P^-1, H_i = M_ik;
-//   the blocks of tile column k + 1 go on to produce the NEXT panel: each rebuilds the updated pivot tile (k+1, k+1) itself, inverts it by 32
-//   scalar sweeps in LDS (repeated by every block of the column, which costs nothing on an otherwise idle chip and saves a launch and a
-//   wait per step) and forms G_i(k+1), H_i(k+1) into the second buffer set
+//   the sweep on pivot block k:   M_ij -= Y_i Y_j^T,  M_ik <- G_i,  M_kj <- G_j^T,  M_kk <- -P^-1   with the panel Y_i = M_ik L^-T, G_i = Y_i L^-1;
+//   the blocks of tile column k + 1 go on to produce the NEXT panel: each rebuilds the updated pivot tile (k+1, k+1) itself, factors it by 32
+//   elimination steps in LDS (repeated by every block of the column, which costs nothing on an otherwise idle chip and saves a launch and a
+//   wait per step) and forms G_i(k+1), Y_i(k+1) into the second buffer set
 // then one pass over the tiles for the traces of W = alpha alpha^T - Ky^-1 against exp(-theta E) and E o exp(-theta E), reduced in a fixed order.
 // n^3 FMAs in all (both triangles are carried: the tiles stay plain dense products), n / 32 + 4 launches: launch-latency-bound below n ~ 500.
 #include "gabo_device.hpp"
@@ -27,7 +34,7 @@ constexpr int kMllB = 32;                  // tile order
 
 struct MllLargeLayout {
     int n, nr, nt, np;                     // training points; Ky padded to nr = ceil(n / b) b; block rows nt = nr / b + 1 (the border's); np = nt b
-    double *M, *G, *H, *Dg, *acc, *part;   // np x np tiles (tile-major: tile (I, J) at ((I nt + J) b b)); two sets of np x b each (G, H: step k reads
+    double *M, *G, *H, *Dg, *acc, *part;   // np x np tiles (tile-major: tile (I, J) at ((I nt + J) b b)); two sets of np x b each (G; H holds Y: step k reads
                                            // set k & 1 and writes the other); two sets of the nt diagonal tiles; 8 doubles; partial sums
     size_t bytes;
     __host__ __device__ double* g(int set, int i) const { return G + ((size_t)set * nt + i) * kMllB * kMllB; }
@@ -78,49 +85,114 @@ __global__ __launch_bounds__(256) void mll_build_kernel(const double* __restrict
     if (blockIdx.x == 0 && threadIdx.x < 8) L.acc[threadIdx.x] = 0.0;
 }
 
-// -P^-1 of the 32 x 32 pivot block in LDS by 32 scalar sweeps (the operator of gp_mll.hip on one tile: every entry updated in parallel,
-// two barriers per pivot); returns (uniformly) whether every pivot was positive, *logdet = sum log pivot.  256 threads, 4 entries each.
-static __device__ __forceinline__ bool sweep_tile(double* P, double* col, double* logdet) {
+constexpr int kMllLd = kMllB + 1;         // row stride of L^-1 in LDS: rows and columns are both read across a wave without bank conflicts
+
+// L^-1 of the 32 x 32 pivot block P = L L^T in LDS: right-looking Cholesky elimination with L^-1 carried along (the scheme of gp_factor.hip on one
+// tile: step k scales column k of the trailing block into l_k and row k of L^-1, then every entry takes its rank-one update in parallel; two
+// barriers per pivot).  P: the block, both triangles given, the lower one overwritten; Li (32 x kMllLd): L^-1 with exact zeros above the diagonal;
+// lk: 32 doubles.  The caller has a barrier between its writes of P and the call.
+// Returns (uniformly) whether every pivot was positive, *logdet = sum log pivot when want_logdet (the pivots are the Schur complements the
+// scalar sweeps meet).
+// 256 threads, 4 entries each.
+static __device__ __forceinline__ bool factor_tile(double* P, double* Li, double* lk, bool want_logdet, double* logdet) {
     const int t = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {                           // identity; no barrier: row 0 is next touched by the thread that wrote it (t = 0),
+        const int q = t + u * 256;                          // every other row after the first barrier below
+        const int a = q / kMllB, b = q - a * kMllB;
+        Li[a * kMllLd + b] = (a == b) ? 1.0 : 0.0;
+    }
     bool ok = true;
-    double mine = 1.0;                                      // thread k keeps pivot k: the logarithms are taken once, after the sweeps
+    double mine = 1.0;                                      // thread k keeps pivot k: the logarithms are taken once, after the elimination
     for (int k = 0; k < kMllB; ++k) {
-        if (t < kMllB) col[t] = P[t * kMllB + k];          // column k (= row k: the tile is symmetric) before it is rewritten
-        __syncthreads();
-        const double p = col[k];
+        const double p = P[k * kMllB + k];                  // (the same value in every thread)
         ok = ok && (p > 0.0);
         mine = (t == k) ? p : mine;
-        const double ip = rcp(p);
+        const double inv = rsqrt_nz(p > 0.0 ? p : 1.0);     // 1 / L[k, k]
+        if (t < kMllB) {
+            lk[t] = (t > k) ? P[t * kMllB + k] * inv : 0.0;
+            if (t <= k) Li[k * kMllLd + t] *= inv;
+        }
+        __syncthreads();
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int q = t + u * 256;
             const int a = q / kMllB, b = q - a * kMllB;
-            const double ca = col[a], cb = col[b];
-            double v;
-            if (a == k && b == k) v = -ip;
-            else if (a == k) v = cb * ip;
-            else if (b == k) v = ca * ip;
-            else v = __builtin_fma(-ca * ip, cb, P[q]);
-            P[q] = v;
+            if (a > k) {
+                const double la = lk[a];
+                if (b > k) {
+                    if (b <= a) P[q] = __builtin_fma(-la, lk[b], P[q]);
+                } else {
+                    Li[a * kMllLd + b] = __builtin_fma(-la, Li[k * kMllLd + b], Li[a * kMllLd + b]);
+                }
+            }
         }
         __syncthreads();
     }
+    *logdet = 0.0;
+    if (!want_logdet) return ok;                            // (block-uniform: only the pivot's own block records it)
     // log det = sum of the logs of the 32 pivots (threads 0..31 = the first half of wave 0), the same value in every thread through LDS
     double ld = (t < kMllB) ? log(mine) : 0.0;
     if (t < 64) {
         for (int off = 32; off > 0; off >>= 1) ld += __shfl_xor(ld, off, 64);
-        if (t == 0) col[0] = ld;
+        if (t == 0) lk[0] = ld;
     }
     __syncthreads();
-    *logdet = col[0];
+    *logdet = lk[0];
     __syncthreads();
     return ok;
 }
 
-// The panel of the FIRST pivot block (k = 0), block row i: P = M_00 -> -P^-1 (every block; block 0 also records log det P and the
-// definiteness flag), G_i = M_i0 P^-1, H_i = M_i0, into set 0.  Later panels are produced by the step kernel of the pivot before.
+// out (global) = -P^-1 = -L^-T L^-1 from Li = L^-1 (LDS): entry (a, b) and entry (b, a) are the same sum, term for term
+static __device__ __forceinline__ void store_neg_inverse(const double* Li, double* __restrict__ out) {
+    for (int q = threadIdx.x; q < kMllB * kMllB; q += blockDim.x) {
+        const int a = q / kMllB, b = q - a * kMllB;
+        double s = 0.0;
+        for (int c = 0; c < kMllB; ++c) s = __builtin_fma(Li[c * kMllLd + a], Li[c * kMllLd + b], s);      // (c < max(a, b): exact zeros)
+        out[q] = -s;
+    }
+}
+
+// The panel of one block row from its tile T = M_ik (LDS) and Li = L^-1 of the pivot block (LDS):  Y = T L^-T -> Hi,  G = Y L^-1 = T P^-1 -> Gi.
+// Y (32 x 32): LDS staging.  Thread -> a 2 x 2 patch of the tile, as in tile_update below (two LDS reads per two FMAs).
+static __device__ __forceinline__ void panel_products(const double* T, const double* Li, double* Y, double* __restrict__ Gi,
+                                                      double* __restrict__ Hi) {
+    const int ta = (threadIdx.x >> 4) * 2, tb = (threadIdx.x & 15) * 2;
+    double s00 = 0.0, s01 = 0.0, s10 = 0.0, s11 = 0.0;
+#pragma unroll 8
+    for (int c = 0; c < kMllB; ++c) {                       // sum_c T[a, c] L^-1[b, c]   (c > b: exact zeros)
+        const double a0 = T[ta * kMllB + c], a1 = T[(ta + 1) * kMllB + c];
+        const double b0 = Li[tb * kMllLd + c], b1 = Li[(tb + 1) * kMllLd + c];
+        s00 = __builtin_fma(a0, b0, s00);
+        s01 = __builtin_fma(a0, b1, s01);
+        s10 = __builtin_fma(a1, b0, s10);
+        s11 = __builtin_fma(a1, b1, s11);
+    }
+    Y[ta * kMllB + tb] = Hi[ta * kMllB + tb] = s00;
+    Y[ta * kMllB + tb + 1] = Hi[ta * kMllB + tb + 1] = s01;
+    Y[(ta + 1) * kMllB + tb] = Hi[(ta + 1) * kMllB + tb] = s10;
+    Y[(ta + 1) * kMllB + tb + 1] = Hi[(ta + 1) * kMllB + tb + 1] = s11;
+    __syncthreads();
+    s00 = s01 = s10 = s11 = 0.0;
+#pragma unroll 8
+    for (int c = 0; c < kMllB; ++c) {                       // sum_c Y[a, c] L^-1[c, b]   (c < b: exact zeros)
+        const double a0 = Y[ta * kMllB + c], a1 = Y[(ta + 1) * kMllB + c];
+        const double b0 = Li[c * kMllLd + tb], b1 = Li[c * kMllLd + tb + 1];
+        s00 = __builtin_fma(a0, b0, s00);
+        s01 = __builtin_fma(a0, b1, s01);
+        s10 = __builtin_fma(a1, b0, s10);
+        s11 = __builtin_fma(a1, b1, s11);
+    }
+    Gi[ta * kMllB + tb] = s00;
+    Gi[ta * kMllB + tb + 1] = s01;
+    Gi[(ta + 1) * kMllB + tb] = s10;
+    Gi[(ta + 1) * kMllB + tb + 1] = s11;
+}
+
+// The panel of the FIRST pivot block (k = 0), block row i: P = M_00 = L L^T (every block; block 0 also stores -P^-1 and records log det P and
+// the definiteness flag), Y_i = M_i0 L^-T, G_i = Y_i L^-1, into set 0.  Later panels are produced by the step kernel of the pivot before.
 __global__ __launch_bounds__(256) void mll_panel_kernel(MllLargeLayout L) {
-    __shared__ __attribute__((aligned(16))) double P[kMllB * kMllB], T[kMllB * kMllB], col[kMllB];
+    __shared__ __attribute__((aligned(16))) double P[kMllB * kMllB], T[kMllB * kMllB], Li[kMllB * kMllLd], col[kMllB];
     const int i = blockIdx.x;
     constexpr int bb = kMllB * kMllB;
     const double* Pk = L.M;
@@ -131,28 +203,19 @@ __global__ __launch_bounds__(256) void mll_panel_kernel(MllLargeLayout L) {
     }
     __syncthreads();
     double logdet;
-    const bool ok = sweep_tile(P, col, &logdet);            // P = -P^-1
+    const bool ok = factor_tile(P, Li, col, i == 0, &logdet);
     if (i == 0) {
-        double* out = L.g(0, 0);
-        for (int q = threadIdx.x; q < bb; q += blockDim.x) out[q] = P[q];
+        store_neg_inverse(Li, L.g(0, 0));
         if (threadIdx.x == 0) {
             L.acc[0] += logdet;
             if (!ok) L.acc[1] = 1.0;
         }
         return;
     }
-    double* Gi = L.g(0, i);
-    double* Hi = L.h(0, i);
-    for (int q = threadIdx.x; q < bb; q += blockDim.x) {
-        const int a = q / kMllB, b = q - a * kMllB;
-        double s = 0.0;
-        for (int c = 0; c < kMllB; ++c) s = __builtin_fma(T[a * kMllB + c], P[c * kMllB + b], s);
-        Gi[q] = -s;                                         // M_i0 P^-1
-        Hi[q] = T[q];
-    }
+    panel_products(T, Li, P, L.g(0, i), L.h(0, i));           // (P: free after the factorisation)
 }
 
-// out (LDS, 32 x 32) = base - Ga Hb^T, or = base when Ga == nullptr.  A, B: LDS staging (B padded: Hb^T is read down a column).
+// out (LDS, 32 x 32) = base - Ga Hb^T.  A, B: LDS staging (B padded: Hb^T is read down a column).
 static __device__ __forceinline__ void tile_update(const double* __restrict__ base, const double* __restrict__ Ga, const double* __restrict__ Hb,
                                                    double* A, double* B, double* out) {
     constexpr int bb = kMllB * kMllB;
@@ -179,10 +242,10 @@ static __device__ __forceinline__ void tile_update(const double* __restrict__ ba
     __syncthreads();
 }
 
-// Step k, tile (i, j): the sweep on pivot block k applied to the tile -  M_ij -= G_i H_j^T,  M_ik <- G_i,  M_kj <- G_j^T,  M_kk <- -P^-1
-// (G, H of set k & 1) - and, in the tile column of the NEXT pivot (j = k + 1, when has_next), that pivot's panel into the other set: the block
+// Step k, tile (i, j): the sweep on pivot block k applied to the tile -  M_ij -= Y_i Y_j^T,  M_ik <- G_i,  M_kj <- G_j^T,  M_kk <- -P^-1
+// (G, Y of set k & 1) - and, in the tile column of the NEXT pivot (j = k + 1, when has_next), that pivot's panel into the other set: the block
 // rebuilds the updated pivot tile itself (from the diagonal copy of the previous step: the tile in M is being rewritten by another block of
-// this launch), inverts it by 32 scalar sweeps, and forms G_i(k+1) = M'_i,k+1 P^-1, H_i(k+1) = M'_i,k+1.  One launch per pivot block.
+// this launch), factors it, and forms Y_i(k+1) = M'_i,k+1 L^-T, G_i(k+1) = Y_i(k+1) L^-1.  One launch per pivot block.
 __global__ __launch_bounds__(256) void mll_step_kernel(MllLargeLayout L, int k, int has_next) {
     __shared__ __attribute__((aligned(16))) double A[kMllB * kMllB], B[kMllB * (kMllB + 1)], Tn[kMllB * kMllB], P[kMllB * kMllB], col[kMllB];
     constexpr int bb = kMllB * kMllB;
@@ -205,7 +268,7 @@ __global__ __launch_bounds__(256) void mll_step_kernel(MllLargeLayout L, int k, 
         }
         __syncthreads();
     } else {
-        tile_update(Tij, L.g(cur, i), L.h(cur, j), A, B, Tn);
+        tile_update(Tij, L.h(cur, i), L.h(cur, j), A, B, Tn);
     }
     for (int q = threadIdx.x; q < bb; q += blockDim.x) {
         Tij[q] = Tn[q];
@@ -218,28 +281,19 @@ __global__ __launch_bounds__(256) void mll_step_kernel(MllLargeLayout L, int k, 
         for (int q = threadIdx.x; q < bb; q += blockDim.x) P[q] = Tn[q];         // this IS the updated pivot tile
         __syncthreads();
     } else {
-        tile_update(L.dg(cur, kn), L.g(cur, kn), L.h(cur, kn), A, B, P);           // (kn != k: the general update of tile (kn, kn))
+        tile_update(L.dg(cur, kn), L.h(cur, kn), L.h(cur, kn), A, B, P);           // (kn != k: the general update of tile (kn, kn))
     }
     double logdet;
-    const bool ok = sweep_tile(P, col, &logdet);            // P = -P^-1
+    const bool ok = factor_tile(P, B, col, i == kn, &logdet);       // B = L^-1 (the staging buffers are free from here on)
     if (i == kn) {
-        double* out = L.g(nxt, kn);
-        for (int q = threadIdx.x; q < bb; q += blockDim.x) out[q] = P[q];
+        store_neg_inverse(B, L.g(nxt, kn));
         if (threadIdx.x == 0) {
             L.acc[0] += logdet;                             // (one writer per step, steps are stream-ordered)
             if (!ok) L.acc[1] = 1.0;
         }
         return;
     }
-    double* Gi = L.g(nxt, i);
-    double* Hi = L.h(nxt, i);
-    for (int q = threadIdx.x; q < bb; q += blockDim.x) {
-        const int a = q / kMllB, b = q - a * kMllB;
-        double s = 0.0;
-        for (int c = 0; c < kMllB; ++c) s = __builtin_fma(Tn[a * kMllB + c], P[c * kMllB + b], s);
-        Gi[q] = -s;
-        Hi[q] = Tn[q];
-    }
+    panel_products(Tn, B, A, L.g(nxt, i), L.h(nxt, i));
 }
 
 // traces of W = alpha alpha^T - Ky^-1 over tile (I, J) of the Ky part: partial sums [W.kb, W.(E o kb), tr W, sum alpha (J == 0 tiles)]

@@ -398,7 +398,8 @@ def test_nested_spd_eigenvalue_constraints_golden(golden):
 
 
 # ---------------------------------------------------------------------------------------------- one-launch marginal likelihood
-@pytest.mark.parametrize("n,power", [(1, 2), (2, 1), (5, 2), (37, 1), (64, 2), (65, 2), (128, 2), (160, 2)])
+@pytest.mark.parametrize("n,power", [(1, 2), (2, 1), (5, 2), (37, 1), (64, 2), (65, 2), (128, 2), (160, 2),
+                                     (30, 2), (31, 1), (39, 2), (40, 1)])       # (the boundaries packed | one wave | several waves)
 def test_gp_mll_kernel_matches_the_oracle(n, power):
     from gabotorch_amd import ops
     from oracle import gp as ogp

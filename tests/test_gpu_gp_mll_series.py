@@ -4,7 +4,8 @@ reference of tests/_cpu_gp_mll_series.py, its bit-level contract with the existi
 Tolerance of the kernel against the reference, per output:  (64 + 8 cond_2(Ky)) 2^-53 x (the sum of the absolute values of that output's terms).
 Every output is a sum of n or n^2 terms whose factors come out of Ky^-1, so an error is relative to the sum of |terms| and amplified by the
 condition number; relative to the RESULT it would be meaningless - with few levels the lengthscale gradient cancels from ~1e7 down to ~0.2.
-The form and the constant 8 are those of tests/test_gpu_gp_condition.py; cond_2(Ky) < 1e4 for every case below."""
+The form and the constant 8 are those of tests/test_gpu_gp_condition.py; cond_2(Ky) < 1e4 for every case below.
+Conditioning beyond 1e4 (up to 1e12) of the sweep bodies this launch shares is covered by tests/test_gpu_gp_ill_conditioned.py."""
 import math
 
 import numpy as np

@@ -1,6 +1,9 @@
 """The three one-call fit entries (gabo_nested_sphere_fit_evaluate, gabo_nested_sphere_fit_evaluate_series, gabo_nested_spd_fit_evaluate) called
 directly through _lib with seeded inputs, against the out_host vectors recorded from the build before the entries shared one host chain
 (tests/golden/nested_fit_entries.npz).  Every entry returned identical bytes on five calls of that build, so the comparison is exact.
+The three cases on the tiled likelihood (n = 190, 190, 170) were recorded again, five identical calls each, when gabo_gp_mll_large began to take
+its pivot blocks in Cholesky-factored form (csrc/gp_mll_large.hip; judged by tests/test_gpu_gp_ill_conditioned.py): they moved by at most 1.5e-11
+of an entry and 3.5e-14 of the largest entry of their vector.  The host chain around that launch is pinned by the other ten.
 
 Shapes - the smallest at which the host chain takes another path: n = 65 is one row past a wave, n = 190 / 170 the tiled likelihood above
 GABO_GP_MLL_MAX_N = 160, n = 1 the degenerate Gram matrix; (21, 18) has 18 projection levels."""
