@@ -25,6 +25,7 @@ def _surrogate_view(gp):
         return gp.base_kernel, float(gp.outputscale), float(gp.mean), gp._train_cache(), gp.train_x
     if type(gp) is models.SingleTaskGP:
         cm = gp.covar_module
+        # (not models._covar_layout: the ScaleKernel class itself, not its name - a namesake reads as a bare kernel - and no numel test)
         base, outputscale = (cm.base_kernel, float(cm.outputscale.detach())) if type(cm) is ScaleKernel else (cm, 1.0)
         linv, alpha, mu = gp._ensure_cache()
         return base, outputscale, float(mu), (linv, alpha), gp.train_x
@@ -47,16 +48,16 @@ class FusedAcquisition:
         device = torch.device(device)
         on = lambda t_: t_ if (t_.device == device and t_.is_contiguous()) else t_.to(device).contiguous()    # noqa: E731
         self.linv = on(linv)
-        # (gabo_gp_factor wrote L^-T next to L^-1: models.*._cache_linv_t, valid for exactly that cache object)
-        held = getattr(acq.model, "_cache_linv_t", None)
-        if held is not None and held[0] is getattr(acq.model, "_cache", None) and held[1].device == self.linv.device:
-            self.linv_t = held[1]
-        else:
+        def held(name):
+            """what the model holds for exactly its current cache object (models._held), if it lies on this device"""
+            t_ = models._held(acq.model, name)
+            return t_ if t_ is not None and t_.device == self.linv.device else None
+        # (gabo_gp_factor wrote L^-T next to L^-1: models.*._cache_linv_t)
+        self.linv_t = held("_cache_linv_t")
+        if self.linv_t is None:
             self.linv_t = self.linv.t().contiguous()
         # (... and the symmetric inverse A = L^-T L^-1, which the fused SPD kernels take in place of the two factors: models.*._cache_kinv)
-        heldk = getattr(acq.model, "_cache_kinv", None)
-        self.kinv = heldk[1] if (heldk is not None and heldk[0] is getattr(acq.model, "_cache", None) and heldk[1] is not None
-                                 and heldk[1].device == self.linv.device) else None
+        self.kinv = held("_cache_kinv")
         self.alpha = on(alpha)
         self.train = on(train_x)
         # d <= 12: value + gradient in ONE launch per evaluation (csrc/spd_acq.hip); the training side is factored once here
@@ -86,11 +87,9 @@ class FusedAcquisition:
         self.metric = {"ai": _lib.GABO_METRIC_AFFINE_INVARIANT, "le": _lib.GABO_METRIC_LOG_EUCLIDEAN, "frob": _lib.GABO_METRIC_FROBENIUS}[flavour]
         self.train_factors = None
         if self.single_launch and family == "spd":
-            # (gabo_spd_gp_prepare wrote them next to the factor: models.ExactGP._cache_factors, valid for exactly that cache object)
-            heldf = getattr(acq.model, "_cache_factors", None)
-            if heldf is not None and heldf[0] is getattr(acq.model, "_cache", None) and heldf[1] is not None and heldf[1].device == self.linv.device:
-                self.train_factors = heldf[1]
-            else:
+            # (gabo_spd_gp_prepare wrote them next to the factor: models.*._cache_factors)
+            self.train_factors = held("_cache_factors")
+            if self.train_factors is None:
                 self.train_factors = ops.spd_acq_prepare_train(self.train)
         if family == "spd" and flavour != "ai":
             # ||0 + 1e-15||_F^2 = d^2 1e-30 (spd_utils_torch.py:156): k(x, x) = 1 to the last bit; logm of the training set once

@@ -122,7 +122,7 @@ class _NestedSpdMllProblem(_OneCallMllProblem):
     it launch by launch (`_evaluate`).  Round 2 differentiated the same launches through torch autograd: 0.3 ms per value, 1.0 ms per gradient
     at n = 10.
     ScaleKernel(NestedSpdLogEuclideanMaternKernel) takes gabo_nested_spd_fit_evaluate_matern (`matern` = nu): the scalar handed to the call is the
-    lengthscale itself and a lengthscale prior is on it; `native = False` issues that chain launch by launch too (`_evaluate_matern`)."""
+    lengthscale itself and a lengthscale prior is on it; `native = False` issues that chain launch by launch too."""
 
     @staticmethod
     def build(model, names, params, manifold):
@@ -169,55 +169,37 @@ class _NestedSpdMllProblem(_OneCallMllProblem):
         return lib.gabo_nested_spd_fit_evaluate(*head, theta, outputscale, noise, mean, want, *buffers), "gabo_nested_spd_fit_evaluate"
 
     def _evaluate(self, theta, outputscale, noise, mean):
+        """One host call where there is one; else the same chain launch by launch: only the Gram launch, the feature gradient and the derivative
+        with respect to the scalar are the kernel's.  Matern: theta is the lengthscale, the feature gradient is formed as autograd forms it (wrt = 1
+        and wrt = 2: the epsilon enters with opposite signs, so the diagonal pair cancels), d / d lengthscale by the distance launch and the
+        element-wise one."""
         from .. import _lib
-        ops = self.ops
         if self._in_one_call():
             return self._one_call(theta, outputscale, noise, mean)
-        if self.matern is not None:
-            return self._evaluate_matern(theta, outputscale, noise, mean)
+        ops, nu, gauss = self.ops, self.matern, _lib.GABO_OUT_GAUSSIAN
         z = ops.spd_project(self.x, self.W)
-        if self.log_euclidean:
-            feat = ops.spd_logm_mandel(z)
-            kb = ops.frobenius_pairwise(feat, feat, theta, _lib.GABO_OUT_GAUSSIAN)
+        feat = ops.spd_logm_mandel(z) if self.log_euclidean or nu is not None else z          # (affine-invariant: the latent points themselves)
+        if nu is not None:
+            kb = ops.flat_matern_pairwise(feat, feat, theta, nu)
         else:
-            kb = ops.spd_ai_pairwise(z, z, theta, _lib.GABO_OUT_GAUSSIAN)
+            kb = (ops.frobenius_pairwise if self.log_euclidean else ops.spd_ai_pairwise)(feat, feat, theta, gauss)
         out, wm = ops.gp_mll_gram(kb, self.y, outputscale, noise, mean, want_w=self.want_grad)
         if not self.want_grad:
             o = out.tolist()
             return o[0], 0.0, o[2], o[3], o[4], o[5]
         gkb = (0.5 * outputscale) * wm                                   # d ll / d kb
-        g_theta = (gkb * torch.xlogy(kb, kb)).sum() / theta              # kb = exp(-theta E):  d kb / d theta = -E kb = kb log(kb) / theta
-        if self.log_euclidean:
-            gfeat = ops.frobenius_backward(feat, feat, gkb, theta, _lib.GABO_OUT_GAUSSIAN, wrt=1) \
-                + ops.frobenius_backward(feat, feat, gkb, theta, _lib.GABO_OUT_GAUSSIAN, wrt=2)
-            gz = ops.spd_logm_mandel_backward(z, gfeat)
+        if nu is not None:
+            gfeat = ops.flat_matern_backward(feat, feat, gkb, theta, nu, wrt=1) + ops.flat_matern_backward(feat, feat, gkb, theta, nu, wrt=2)
+            dist = ops.frobenius_pairwise(feat, feat, 1.0, _lib.GABO_OUT_DISTANCE)
+            g_theta = (gkb * ops.flat_matern_from_distance(dist, theta, nu, order=1)).sum()
         else:
-            gz = ops.spd_ai_backward(z, z, gkb, theta, _lib.GABO_OUT_GAUSSIAN, wrt=1) + ops.spd_ai_backward(z, z, gkb, theta, _lib.GABO_OUT_GAUSSIAN, wrt=2)
+            g_theta = (gkb * torch.xlogy(kb, kb)).sum() / theta          # kb = exp(-theta E):  d kb / d theta = -E kb = kb log(kb) / theta
+            backward = ops.frobenius_backward if self.log_euclidean else ops.spd_ai_backward
+            gfeat = backward(feat, feat, gkb, theta, gauss, wrt=1) + backward(feat, feat, gkb, theta, gauss, wrt=2)
+        gz = gfeat if feat is z else ops.spd_logm_mandel_backward(z, gfeat)
         gm = ops.mandel_to_matrix(gz)                                    # n x d x d (symmetric)
         gw = 2.0 * torch.einsum("nab,bc,ncd->ad", self.xm, self.W, gm)
         flat = torch.cat([out, g_theta.reshape(1), gw.reshape(-1)]).tolist()          # one read-back
-        self.tail = np.asarray(flat[7:])
-        return flat[0], flat[6], flat[2], flat[3], flat[4], flat[5]
-
-    def _evaluate_matern(self, lengthscale, outputscale, noise, mean):
-        """gabo_nested_spd_fit_evaluate_matern's chain launch by launch: the feature gradient as autograd forms it (wrt = 1 and wrt = 2: the
-        epsilon enters with opposite signs, so the diagonal pair cancels), d / d lengthscale by the distance launch and the element-wise one."""
-        from .. import _lib
-        ops, nu = self.ops, self.matern
-        z = ops.spd_project(self.x, self.W)
-        feat = ops.spd_logm_mandel(z)
-        kb = ops.flat_matern_pairwise(feat, feat, lengthscale, nu)
-        out, wm = ops.gp_mll_gram(kb, self.y, outputscale, noise, mean, want_w=self.want_grad)
-        if not self.want_grad:
-            o = out.tolist()
-            return o[0], 0.0, o[2], o[3], o[4], o[5]
-        gkb = (0.5 * outputscale) * wm                                   # d ll / d kb
-        gfeat = ops.flat_matern_backward(feat, feat, gkb, lengthscale, nu, wrt=1) + ops.flat_matern_backward(feat, feat, gkb, lengthscale, nu, wrt=2)
-        dist = ops.frobenius_pairwise(feat, feat, 1.0, _lib.GABO_OUT_DISTANCE)
-        g_ls = (gkb * ops.flat_matern_from_distance(dist, lengthscale, nu, order=1)).sum()
-        gm = ops.mandel_to_matrix(ops.spd_logm_mandel_backward(z, gfeat))          # n x d x d (symmetric)
-        gw = 2.0 * torch.einsum("nab,bc,ncd->ad", self.xm, self.W, gm)
-        flat = torch.cat([out, g_ls.reshape(1), gw.reshape(-1)]).tolist()          # one read-back
         self.tail = np.asarray(flat[7:])
         return flat[0], flat[6], flat[2], flat[3], flat[4], flat[5]
 

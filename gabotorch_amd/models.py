@@ -9,6 +9,7 @@ EI(maximize=False): sigma = sqrt(clamp_min(var, 1e-9)), u = -(mu - best_f)/sigma
 The small dense linear algebra here (n_train <= a few hundred) is torch; the kernel evaluations and their gradients are
 the HIP kernels.
 """
+import functools
 import math
 import warnings
 
@@ -174,6 +175,50 @@ def _install_caches(model, cache, linv_t, kinv, factors):
         model._cache_factors = (cache, factors)
 
 
+def _device_cache(model, base_kernel, outputscale, noise, mean, tail=(), matrix_only=False):
+    """Fills the caches of `model` from ONE launch instead of Cholesky (+ its info read-back), cholesky_solve and a triangular solve:
+    `_cache` = (L^-1, alpha) + tail, with L^-T and the symmetric inverse tied to it.  An affine-invariant kernel on one set of matrices that
+    fit the registers takes ops.spd_gp_prepare - what its forward launches (the x1-is-x2 build), the factor and the fused evaluators' training
+    factors from one host call - any other kernel its own forward, then ops.gp_factor (csrc/gp_factor.hip).  A factor that does not exist
+    drops all four caches again: ops.check_deferred calls `on_fail` before it raises.  matrix_only: a batch of Gram matrices installs nothing."""
+    from .kernel_utils import kernels_spd as _ks
+    x, factors = model.train_x, None
+    drop = functools.partial(_drop_caches, model)
+    with torch.no_grad():
+        if type(base_kernel) in (_ks.SpdAffineInvariantGaussianKernel, _ks.SpdAffineInvariantLaplaceKernel) and x.dim() == 2 \
+                and x.shape[-1] <= _l.GABO_SPD_REG_MAX_DIM * (_l.GABO_SPD_REG_MAX_DIM + 1) // 2:
+            mode = _l.GABO_OUT_GAUSSIAN if type(base_kernel) is _ks.SpdAffineInvariantGaussianKernel else _l.GABO_OUT_LAPLACE
+            linv, linv_t, alpha, factors, kinv = _ops.spd_gp_prepare(x, model.train_y, base_kernel.beta_float(), mode, outputscale, noise, mean, on_fail=drop)
+        else:
+            kb = base_kernel.forward(x, x)
+            if matrix_only and kb.dim() != 2:
+                return
+            linv, linv_t, alpha, kinv = _ops.gp_factor(kb.double(), model.train_y, outputscale, noise, mean, defer_check=True, on_fail=drop, want_kinv=True)
+    _install_caches(model, (linv, alpha) + tail, linv_t, kinv, factors)
+
+
+def _torch_cache(ky, y, mean):
+    """(L^-1, alpha) of Ky = outputscale K + noise I through torch.linalg: any size, any device.  L^-1 once: the per-call triangular solve
+    becomes a GEMM (rocBLAS trsm allocates workspace, which a hipGraph capture of the acquisition evaluation does not allow)."""
+    L = torch.linalg.cholesky(ky)
+    alpha = torch.cholesky_solve((y.to(L.device) - mean).unsqueeze(-1), L).squeeze(-1)
+    return torch.linalg.solve_triangular(L, torch.eye(L.shape[-1], dtype=L.dtype, device=L.device), upper=False), alpha
+
+
+def _marginal_posterior(kernel, train_x, linv, alpha, X):
+    """X: b x 1 x d (or b x d) -> (mean b WITHOUT the constant, variance b); kernel(X1, X2): the scaled kernel matrix.  Differentiable in X."""
+    if X.dim() == 2:
+        X = X.unsqueeze(-2)
+    b = X.shape[0]
+    xt = train_x.to(X.device).expand(b, *train_x.shape)                     # stride-0 batch: factored once by the kernel
+    ks = kernel(X, xt).squeeze(-2)                                          # b x n   (candidates first)
+    kss = kernel(X, X)                                                      # b x 1 x 1
+    Li, ad = linv.to(ks.device), alpha.to(ks.device)
+    mean = ks @ ad
+    v = ks @ Li.transpose(-1, -2)                                           # b x n  = (L^-1 ks^T)^T
+    return mean, kss.reshape(b) - (v * v).sum(-1)
+
+
 class ExactGP(torch.nn.Module):
     def __init__(self, train_x, train_y, base_kernel, outputscale=1.0, noise=1e-2, mean=None):
         super().__init__()
@@ -192,63 +237,21 @@ class ExactGP(torch.nn.Module):
         if self._cache is None:
             n = self.train_x.shape[-2]
             if self.train_x.is_cuda and 0 < n <= _l.GABO_GP_FACTOR_MAX_N:
-                # one launch instead of Cholesky (+ its info read-back), cholesky_solve and a triangular solve (csrc/gp_factor.hip)
-                def drop(model=self):
-                    # (the factor this cache was to hold does not exist: ops.check_deferred calls this before it raises)
-                    model._cache = None
-                    model._cache_linv_t = None
-                    model._cache_factors = None
-                    model._cache_kinv = None
+                # the cache is the pair (L^-1, alpha); whatever the kernel returns goes to the launch (no guard against a batch of matrices)
+                _device_cache(self, self.base_kernel, float(self.outputscale), float(self.noise), float(self.mean))
+            else:
                 with torch.no_grad():
-                    from .kernel_utils import kernels_spd as _ks
-                    bk = self.base_kernel
-                    if type(bk) in (_ks.SpdAffineInvariantGaussianKernel, _ks.SpdAffineInvariantLaplaceKernel) and self.train_x.dim() == 2 \
-                            and self.train_x.shape[-1] <= _l.GABO_SPD_REG_MAX_DIM * (_l.GABO_SPD_REG_MAX_DIM + 1) // 2:
-                        # (what bk.forward launches - the x1-is-x2 build - then the factor and the fused evaluators' training factors: one host call)
-                        mode = _l.GABO_OUT_GAUSSIAN if type(bk) is _ks.SpdAffineInvariantGaussianKernel else _l.GABO_OUT_LAPLACE
-                        Linv, Linv_t, alpha, factors, kinv = _ops.spd_gp_prepare(self.train_x, self.train_y, bk.beta_float(), mode, float(self.outputscale),
-                                                                                 float(self.noise), float(self.mean), on_fail=drop)
-                        self._cache = (Linv, alpha)
-                        self._cache_linv_t = (self._cache, Linv_t)
-                        self._cache_factors = (self._cache, factors)
-                        self._cache_kinv = (self._cache, kinv)
-                        return self._cache
-                    kb = bk.forward(self.train_x, self.train_x).double()
-                    Linv, Linv_t, alpha, kinv = _ops.gp_factor(kb, self.train_y, float(self.outputscale), float(self.noise), float(self.mean), defer_check=True,
-                                                               on_fail=drop, want_kinv=True)
-                self._cache = (Linv, alpha)
-                self._cache_linv_t = (self._cache, Linv_t)
-                self._cache_kinv = (self._cache, kinv)
-                return self._cache
-            with torch.no_grad():
-                k = self.outputscale * self.base_kernel.forward(self.train_x, self.train_x)
-                n = k.shape[-1]
-                k = k + self.noise * torch.eye(n, dtype=k.dtype, device=k.device)
-                L = torch.linalg.cholesky(k)
-                alpha = torch.cholesky_solve((self.train_y.to(k.device) - self.mean).unsqueeze(-1), L).squeeze(-1)
-                # L^-1 once: the per-call triangular solve becomes a GEMM (rocBLAS trsm allocates workspace, which a hipGraph
-                # capture of the acquisition evaluation does not allow)
-                Linv = torch.linalg.solve_triangular(L, torch.eye(n, dtype=L.dtype, device=L.device), upper=False)
-            self._cache = (Linv, alpha)
+                    k = self.outputscale * self.base_kernel.forward(self.train_x, self.train_x)
+                    k = k + self.noise * torch.eye(k.shape[-1], dtype=k.dtype, device=k.device)
+                    self._cache = _torch_cache(k, self.train_y, self.mean)
         return self._cache
 
     def posterior(self, X):
         """X: b x 1 x d  ->  (mean b, variance b)."""
-        if X.dim() == 2:
-            X = X.unsqueeze(-2)
-        b = X.shape[0]
         Linv, alpha = self._train_cache()
-        from . import ops as _ops
         _ops.check_deferred()
-        xt = self.train_x.to(X.device).expand(b, *self.train_x.shape)           # stride-0 batch: factored once by the kernel
-        ks = self.outputscale * self.base_kernel.forward(X, xt)                 # b x 1 x n   (candidates first)
-        kss = self.outputscale * self.base_kernel.forward(X, X)                 # b x 1 x 1
-        ks = ks.squeeze(-2)
-        Li, ad = Linv.to(ks.device), alpha.to(ks.device)
-        mean = self.mean + ks @ ad
-        v = ks @ Li.transpose(-1, -2)                                           # b x n  = (L^-1 ks^T)^T
-        var = kss.reshape(b) - (v * v).sum(-1)
-        return mean, var
+        mean, var = _marginal_posterior(lambda x1, x2: self.outputscale * self.base_kernel.forward(x1, x2), self.train_x, Linv, alpha, X)
+        return self.mean + mean, var
 
     def forward(self, X):
         """`model(x_test)`: the joint posterior of the latent f (no observation noise) over the test set X (m x d_vec) as a
@@ -412,6 +415,28 @@ class _ExactMll(torch.autograd.Function):
         return (gk, None) + tuple(scalars[i].to(dev_, dt_) for i, (dev_, dt_) in enumerate(ctx.host))
 
 
+def _covar_layout(cm):
+    """How a covariance module is read -> (kind, base kernel): "bare", a kernel on its own (the base is `cm`); "scaled", a ScaleKernel - the
+    stand-in's or gpytorch's, told by its class name - with ONE outputscale around a base kernel; "other", any other wrapper of a base_kernel
+    (batched outputscales, a foreign class), which the likelihood and the prediction evaluate as a whole and the fast fits do not take."""
+    base = getattr(cm, "base_kernel", None)
+    if base is None:
+        return "bare", cm
+    return ("scaled" if type(cm).__name__ == "ScaleKernel" and cm.raw_outputscale.numel() == 1 else "other"), base
+
+
+def _outputscale_fn(cm, kind):
+    """() -> the outputscale of a "scaled" or "bare" covariance module as a 0-d fp64 tensor"""
+    if kind == "scaled":
+        return lambda: cm.outputscale.double().reshape(())
+    return lambda: torch.ones((), dtype=torch.float64)
+
+
+def _plus_priors(ll, pri):
+    """ll + log priors, which are a tensor on the parameters' device or - no prior at all - the float 0.0"""
+    return ll + (pri.to(ll.device) if torch.is_tensor(pri) else pri)
+
+
 class SingleTaskGP(torch.nn.Module):
     """Constant-mean exact GP with a Gaussian likelihood and trainable hyper-parameters, laid out like the models of the
     reference examples (examples/gabo_spd.py:165-176: ScaleKernel(base, outputscale_prior=Gamma(2, .15)), noise prior
@@ -444,8 +469,8 @@ class SingleTaskGP(torch.nn.Module):
 
     def _priors(self):
         total = 0.0
-        mods = [self.covar_module] + ([self.covar_module.base_kernel] if hasattr(self.covar_module, "base_kernel") else [])
-        for m in mods:
+        kind, base = _covar_layout(self.covar_module)
+        for m in ([self.covar_module] if kind == "bare" else [self.covar_module, base]):
             for _, (prior, closure, _) in getattr(m, "_priors", {}).items():
                 total = total + prior.log_prob(closure()).sum()
         if self.noise_prior is not None:
@@ -459,13 +484,12 @@ class SingleTaskGP(torch.nn.Module):
         itself (its own HIP backward); above that, torch's Cholesky / solve."""
         from . import _lib
         cm = self.covar_module
-        scaled = hasattr(cm, "base_kernel") and type(cm).__name__ == "ScaleKernel" and cm.raw_outputscale.numel() == 1
-        kb = (cm.base_kernel if scaled else cm).forward(self.train_x, self.train_x)
+        kind, base = _covar_layout(cm)
+        kb = (base if kind == "scaled" else cm).forward(self.train_x, self.train_x)
         if kb.is_cuda and kb.dim() == 2 and kb.shape[-1] <= _lib.GABO_GP_MLL_LARGE_MAX_N:
-            os_ = cm.outputscale.double().reshape(()) if scaled else torch.ones((), dtype=torch.float64)
+            os_ = _outputscale_fn(cm, kind)()
             ll = _ExactMll.apply(kb.double(), self.train_y.to(kb.device), os_, self.noise.reshape(()), self.mean_constant.reshape(()))
-            pri = self._priors()
-            return (ll + (pri.to(ll.device) if torch.is_tensor(pri) else pri)) / kb.shape[-1]
+            return _plus_priors(ll, self._priors()) / kb.shape[-1]
         return self._marginal_log_likelihood_torch()
 
     def _marginal_log_likelihood_torch(self):
@@ -476,8 +500,7 @@ class SingleTaskGP(torch.nn.Module):
         r = (self.train_y.to(k.device) - self.mean_constant.to(k.device)).unsqueeze(-1)
         alpha = torch.cholesky_solve(r, L)
         ll = -0.5 * (r * alpha).sum() - torch.log(torch.diagonal(L)).sum() - 0.5 * n * math.log(2 * math.pi)
-        pri = self._priors()
-        return (ll + (pri.to(ll.device) if torch.is_tensor(pri) else pri)) / n
+        return _plus_priors(ll, self._priors()) / n
 
     def invalidate(self):
         self._cache = None
@@ -502,14 +525,10 @@ class SingleTaskGP(torch.nn.Module):
         parameters inside the distance, batched hyper-parameters, more than GABO_GP_MLL_LARGE_MAX_N points)."""
         from . import _lib
         from .kernel_utils import kernel_parameters
-        cm = self.covar_module
-        base = getattr(cm, "base_kernel", None)
-        if base is None:
-            base, os_fn = cm, (lambda: torch.ones((), dtype=torch.float64))
-        elif type(cm).__name__ == "ScaleKernel" and cm.raw_outputscale.numel() == 1:
-            os_fn = lambda: cm.outputscale.double().reshape(())                                # noqa: E731
-        else:
+        kind, base = _covar_layout(self.covar_module)
+        if kind == "other":
             return None
+        os_fn = _outputscale_fn(self.covar_module, kind)
         x = self.train_x
         if x.dim() != 2 or not 1 <= x.shape[0] <= _lib.GABO_GP_MLL_LARGE_MAX_N:
             return None
@@ -533,14 +552,10 @@ class SingleTaskGP(torch.nn.Module):
         the differentiable route of ops.sphere_matern_kernel forms, so the value agrees with marginal_log_likelihood() to rounding."""
         from . import _lib, ops
         from .kernel_utils.kernels_sphere import SphereRiemannianMaternKernel
-        cm = self.covar_module
-        base = getattr(cm, "base_kernel", None)
-        if base is None:
-            base, os_fn = cm, (lambda: torch.ones((), dtype=torch.float64))
-        elif type(cm).__name__ == "ScaleKernel" and cm.raw_outputscale.numel() == 1:
-            os_fn = lambda: cm.outputscale.double().reshape(())                                # noqa: E731
-        else:
+        kind, base = _covar_layout(self.covar_module)
+        if kind == "other":
             return None
+        os_fn = _outputscale_fn(self.covar_module, kind)
         x = self.train_x
         if type(base) is not SphereRiemannianMaternKernel or x.dim() != 2 or not 1 <= x.shape[0] <= _lib.GABO_GP_MLL_LARGE_MAX_N:
             return None
@@ -559,14 +574,10 @@ class SingleTaskGP(torch.nn.Module):
         GABO_OUT_DISTANCE launch writes on the features the kernel's forward forms."""
         from . import _lib, ops
         from .kernel_utils import kernels_spd as _ks
-        cm = self.covar_module
-        base = getattr(cm, "base_kernel", None)
-        if base is None:
-            base, os_fn = cm, (lambda: torch.ones((), dtype=torch.float64))
-        elif type(cm).__name__ == "ScaleKernel" and cm.raw_outputscale.numel() == 1:
-            os_fn = lambda: cm.outputscale.double().reshape(())                                # noqa: E731
-        else:
+        kind, base = _covar_layout(self.covar_module)
+        if kind == "other":
             return None
+        os_fn = _outputscale_fn(self.covar_module, kind)
         x = self.train_x
         if type(base) not in (_ks.SpdLogEuclideanMaternKernel, _ks.SpdFrobeniusMaternKernel) or x.dim() != 2 \
                 or not 1 <= x.shape[0] <= _lib.GABO_GP_MLL_LARGE_MAX_N:
@@ -600,7 +611,7 @@ class SingleTaskGP(torch.nn.Module):
             return (lambda ls, os_, noise, mean: ops.gp_mll_matern(r, y, ls, nu, os_, noise, mean)), ls_fn, os_fn, True
         c, coeff_fn, os_fn = form
         y = self.train_y.to(c.device).contiguous()
-        base = getattr(self.covar_module, "base_kernel", self.covar_module)
+        base = _covar_layout(self.covar_module)[1]
         kappa_fn = lambda: base.lengthscale.double().reshape(())                               # noqa: E731
         return (lambda kappa, os_, noise, mean: ops.gp_mll_series(c, y, *coeff_fn(kappa), os_, noise, mean)), kappa_fn, os_fn, True
 
@@ -622,8 +633,7 @@ class SingleTaskGP(torch.nn.Module):
             pri = self._priors()
             value = (ll + (pri.item() if torch.is_tensor(pri) else pri)) / n
             # a linear stand-in with the same first derivatives as ll at this point, so that autograd does the chain rule
-            proxy = (g_theta * theta + g_os * os_.to(theta.device) + g_noise * noise.to(theta.device)
-                     + g_mean * mean.to(theta.device) + (pri.to(theta.device) if torch.is_tensor(pri) else 0.0)) / n
+            proxy = _plus_priors(g_theta * theta + g_os * os_.to(theta.device) + g_noise * noise.to(theta.device) + g_mean * mean.to(theta.device), pri) / n
             return value, proxy
 
         return evaluate
@@ -649,7 +659,7 @@ class SingleTaskGP(torch.nn.Module):
                 return None
             evaluator, series = form[0], form[3]
         cm = self.covar_module
-        base = getattr(cm, "base_kernel", cm)
+        base = _covar_layout(cm)[1]
         index = {id(p): i for i, p in enumerate(params)}
         plan = {}                      # hyper-parameter -> (position in v, fp32?, lower bound)
 
@@ -712,75 +722,28 @@ class SingleTaskGP(torch.nn.Module):
 
     def _ensure_cache(self):
         """(L^-1, alpha, mean) of the fitted model; freezes the kernel hyper-parameters (prediction mode)."""
-        if self._cache is None:
-            self._factor_in_one_launch()
+        from . import _compat
+        cm, n = self.covar_module, self.train_x.shape[-2]
+        # the one-launch route only for the stand-in ScaleKernel(base), by its class and without gpytorch: a bare kernel, too, goes to torch
+        if self._cache is None and self.train_x.is_cuda and 0 < n <= _l.GABO_GP_FACTOR_MAX_N and type(cm) is _compat.ScaleKernel \
+                and not _compat.HAVE_GPYTORCH:
+            mu = self.mean_constant.detach().to(self.train_x.device)
+            # the cache is the triple (L^-1, alpha, mu); a batch of Gram matrices leaves it empty, for torch to fill
+            _device_cache(self, cm.base_kernel, float(cm.outputscale.detach()), float(self.noise.detach()), float(mu), (mu,), matrix_only=True)
         if self._cache is None:
             with torch.no_grad():
-                L = torch.linalg.cholesky(self._kxx())
-                mu = self.mean_constant.detach().to(L.device)
-                alpha = torch.cholesky_solve((self.train_y.to(L.device) - mu).unsqueeze(-1), L).squeeze(-1)
-                Linv = torch.linalg.solve_triangular(L, torch.eye(L.shape[-1], dtype=L.dtype, device=L.device), upper=False)
-            self._cache = (Linv, alpha, mu)
-        for p in self.covar_module.parameters():
+                ky = self._kxx()
+                mu = self.mean_constant.detach().to(ky.device)
+                self._cache = _torch_cache(ky, self.train_y, mu) + (mu,)
+        for p in self.covar_module.parameters():                    # on every call, not only when the cache is built
             p.requires_grad_(False)
         return self._cache
 
-    def _factor_in_one_launch(self):
-        """gabo_gp_factor for the plain ScaleKernel(base) / base covariance modules on a HIP device (csrc/gp_factor.hip); leaves the cache
-        empty otherwise (the torch route below then fills it)."""
-        from . import _compat, _lib as _l, ops as _ops
-        cm = self.covar_module
-        n = self.train_x.shape[-2]
-        if not (self.train_x.is_cuda and 0 < n <= _l.GABO_GP_FACTOR_MAX_N):
-            return
-        if type(cm) is _compat.ScaleKernel and not _compat.HAVE_GPYTORCH:
-            base, outputscale = cm.base_kernel, float(cm.outputscale.detach())
-        else:
-            return
-        def drop(model=self):
-            model._cache = None
-            model._cache_linv_t = None
-            model._cache_kinv = None
-            model._cache_factors = None
-        from .kernel_utils import kernels_spd as _ks
-        if type(base) in (_ks.SpdAffineInvariantGaussianKernel, _ks.SpdAffineInvariantLaplaceKernel) and self.train_x.dim() == 2 \
-                and self.train_x.shape[-1] <= _l.GABO_SPD_REG_MAX_DIM * (_l.GABO_SPD_REG_MAX_DIM + 1) // 2:
-            # (as models.ExactGP: Gram of the training set, factor, symmetric inverse and the fused evaluators' training factors from ONE host call)
-            with torch.no_grad():
-                mu = self.mean_constant.detach().to(self.train_x.device)
-                mode = _l.GABO_OUT_GAUSSIAN if type(base) is _ks.SpdAffineInvariantGaussianKernel else _l.GABO_OUT_LAPLACE
-                Linv, Linv_t, alpha, factors, kinv = _ops.spd_gp_prepare(self.train_x, self.train_y, base.beta_float(), mode, outputscale,
-                                                                         float(self.noise.detach()), float(mu), on_fail=drop)
-            self._cache = (Linv, alpha, mu)
-            self._cache_linv_t = (self._cache, Linv_t)
-            self._cache_kinv = (self._cache, kinv)
-            self._cache_factors = (self._cache, factors)
-            return
-        with torch.no_grad():
-            kb = base.forward(self.train_x, self.train_x)
-            if kb.dim() != 2:
-                return
-            mu = self.mean_constant.detach().to(kb.device)
-            Linv, Linv_t, alpha, kinv = _ops.gp_factor(kb.double(), self.train_y, outputscale, float(self.noise.detach()), float(mu), defer_check=True,
-                                                       on_fail=drop, want_kinv=True)
-        self._cache = (Linv, alpha, mu)
-        self._cache_linv_t = (self._cache, Linv_t)
-        self._cache_kinv = (self._cache, kinv)
-
     def posterior(self, X):
-        if X.dim() == 2:
-            X = X.unsqueeze(-2)
-        b = X.shape[0]
         Linv, alpha, mu = self._ensure_cache()
-        from . import ops as _ops
         _ops.check_deferred()
-        xt = self.train_x.to(X.device).expand(b, *self.train_x.shape)
-        ks = self.covar_module.forward(X, xt).squeeze(-2)
-        kss = self.covar_module.forward(X, X).reshape(b)
-        Li, ad = Linv.to(ks.device), alpha.to(ks.device)
-        mean = mu.to(ks.device) + ks @ ad
-        v = ks @ Li.transpose(-1, -2)
-        return mean, kss - (v * v).sum(-1)
+        mean, var = _marginal_posterior(self.covar_module.forward, self.train_x, Linv, alpha, X)
+        return mu.to(mean.device) + mean, var
 
     def forward(self, X):
         """`preds = model(x_test)` of the reference's GP-regression demos (examples/kernels/spd/spd_kernels.py:168): the joint posterior of
@@ -788,16 +751,13 @@ class SingleTaskGP(torch.nn.Module):
         covariance module's own launches (any kernel of the library), the rest from ops.gp_posterior_joint.  Freezes the hyper-parameters
         like posterior(); no autograd through the prediction."""
         Linv, alpha, mu = self._ensure_cache()
-        from . import ops as _ops
         _ops.check_deferred()
         base, outputscale = self._base_and_outputscale()
         return _joint_posterior(base, outputscale, self.train_x, Linv, alpha, float(mu), X)
 
     def _base_and_outputscale(self):
-        cm = self.covar_module
-        if hasattr(cm, "base_kernel") and type(cm).__name__ == "ScaleKernel" and cm.raw_outputscale.numel() == 1:
-            return cm.base_kernel, float(cm.outputscale.detach())
-        return cm, 1.0
+        kind, base = _covar_layout(self.covar_module)
+        return (base, float(self.covar_module.outputscale.detach())) if kind == "scaled" else (self.covar_module, 1.0)
 
     def condition_on_observations(self, X, Y=None):
         """As ExactGP.condition_on_observations: a new SingleTaskGP for prediction over the training set extended by X (t x d_vec) with
