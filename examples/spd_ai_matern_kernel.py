@@ -3,8 +3,9 @@
 flow of examples/spd_matern_kernel.py (the C-shaped trajectory of the 2D-letters data as 2 x 2 SPD matrices, time as the target, a part of the
 trajectory left out of the training set) with SpdAffineInvariantMaternKernel.  The kernel has no closed form; it is evaluated through random
 phase features (one small Cholesky factorisation per point and feature, on the device), a Monte-Carlo approximation with error
-O(1 / sqrt(num_features)) that is positive semi-definite for EVERY lengthscale.  The surrogate is fitted by autograd - the log-diagonals once,
-then element-wise work per L-BFGS evaluation - and `model(x_test)` gives the joint posterior over the whole trajectory.
+O(1 / sqrt(num_features)) that is positive semi-definite for EVERY lengthscale.  `fit_gpytorch_model` takes the one-call route for this kernel
+without any change here (SingleTaskGP._spectral_form: the log-diagonals once, then one gabo_gp_mll_spd_ai_spectral call per L-BFGS
+evaluation; fast=False keeps autograd), and `model(x_test)` gives the joint posterior over the whole trajectory.
 
 The second part is a table of the smallest eigenvalue of the Gram matrix by lengthscale, beside SpdAffineInvariantGaussianKernel by beta: the
 Gaussian kernel of the same metric is positive definite only from some beta upwards (its `beta_min`), the Matern family has no such range.

@@ -135,6 +135,12 @@ SIGNATURES = {
     "gabo_gp_mll_matern": (_I, [_P, _P, _I64, _D, _I, _D, _D, _D, _P, _P]),
     "gabo_spd_ai_logdiag": (_I, [_P, _P, _P, _I64, _I64, _I, _P]),
     "gabo_spd_ai_spectral_features": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I, _P]),
+    "gabo_spd_ai_spectral_points_dkappa": (_I, [_P, _P, _I64, _I, _D, _D, _P, _P, _P, _P, _P]),
+    "gabo_spd_ai_spectral_features_dkappa": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I, _P]),
+    "gabo_spd_ai_feature_gram_workspace_bytes": (_SZ, [_I64, _I64]),
+    "gabo_spd_ai_feature_gram": (_I, [_P, _P, _I64, _I64, _P, _SZ, _P]),
+    "gabo_gp_mll_spd_ai_spectral_workspace_bytes": (_SZ, [_I64, _I64, _I]),
+    "gabo_gp_mll_spd_ai_spectral": (_I, [_P, _P, _P, _P, _I64, _I64, _I, _D, _D, _D, _D, _D, _P, _P, _SZ, _P, _SZ, _P]),
     "gabo_gram_extreme_eig_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "gabo_gram_extreme_eig": (_I, [_P, _I64, _I64, _P, _I64, _P, _P, _SZ, _P]),
     "gabo_gp_posterior_joint_workspace_bytes": (_SZ, [_I64, _I64]),

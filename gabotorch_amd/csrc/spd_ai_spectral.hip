@@ -12,14 +12,12 @@
 // One operation order whatever the launch shape, every multiply-add a spelled-out fma: the bits of a(i, l) depend on X_i and H_l only.
 // A NaN or non-SPD X_i (Cholesky pivot not > 0) makes G, and with it every output of row i, NaN; nothing is reported.
 #include "gabo_device.hpp"
+#include "spd_ai_spectral_value.hpp"
 #include "../../include/gabo_hip.h"
 
 #include <cmath>
 
 namespace gabo {
-
-constexpr int kSpectralBlock = 128;          // lanes = features per block
-constexpr int kSpectralMaxDim = 10;
 
 // chol(X_i) -> Gs (packed lower triangle, tri(r, c)), computed row by row in registers by the first wave (every lane on the same values).
 template <int D>
@@ -84,18 +82,6 @@ __device__ __forceinline__ void spectral_logdiag_lane(const double* __restrict__
             static_for<D>([&](auto jj) { constexpr int j = decltype(jj)::value; v[k * D + j] = m[j]; });
         }
     });
-}
-
-// sqrt(w) exp(la) (cos theta, sin theta).  Not inlined: inside the feature loop hipcc would hoist the constants of exp and sincos out of
-// the loop and hold them in registers through the factorisation (70 VGPRs at d = 10).
-struct SpectralPair {
-    double c, s;
-};
-__device__ __attribute__((noinline)) SpectralPair spectral_feature_value(double theta, double la, double w) {
-    const double amp = __builtin_sqrt(w) * exp(la);
-    double sn, cs;
-    sincos(theta, &sn, &cs);
-    return {amp * cs, amp * sn};
 }
 
 // blockIdx.x = point * chunks + chunk of kSpectralBlock features; out (n, L, d)

@@ -590,11 +590,32 @@ class SingleTaskGP(torch.nn.Module):
             r = ops.frobenius_pairwise(feat, feat, 1.0, _lib.GABO_OUT_DISTANCE).contiguous()
         return r, (lambda: base.lengthscale.double().reshape(())), base.nu, os_fn
 
+    def _spectral_form(self):
+        """(A, base draw, lengthscale_fn, nu, outputscale_fn) when the covariance is [ScaleKernel of] SpdAffineInvariantMaternKernel: random
+        phase features of the log-diagonals A = ops.spd_ai_logdiag of the training points, which are fixed during a fit while the spectral
+        points and weights move with the lengthscale (ops.gp_mll_spd_ai_spectral); None for anything else, a batched lengthscale, dim > 10 or
+        more than GABO_GP_MLL_LARGE_MAX_N points.  A comes from the kernel's own _logdiag: the one launch per point set stays one."""
+        from . import _lib, ops
+        from .kernel_utils.kernels_spd import SpdAffineInvariantMaternKernel
+        kind, base = _covar_layout(self.covar_module)
+        if kind == "other":
+            return None
+        os_fn = _outputscale_fn(self.covar_module, kind)
+        x = self.train_x
+        if type(base) is not SpdAffineInvariantMaternKernel or x.dim() != 2 or not 1 <= x.shape[0] <= _lib.GABO_GP_MLL_LARGE_MAX_N:
+            return None
+        if base.raw_lengthscale.numel() != 1 or base.dim > 10 or x.shape[-1] != base.dim * (base.dim + 1) // 2:
+            return None
+        with torch.no_grad():
+            dev = ops._device_for(x)
+            a = base._logdiag(x, base._phases_on(dev)).to(dev).contiguous()
+        return a, base.spectral_base, (lambda: base.lengthscale.double().reshape(())), base.nu, os_fn
+
     def _fast_evaluator(self):
         """(launch(parameter, outputscale, noise, mean) -> the six numbers of ops.gp_mll, parameter_fn, outputscale_fn, series?) on the matrix
         that is fixed during a fit: the exponent matrix of a plain kernel (parameter theta), else the inner products of the sphere Matern
-        kernel or the distances of a flat SPD Matern kernel (parameter: the lengthscale itself, `series`); None when the model has none of
-        the three forms."""
+        kernel, the distances of a flat SPD Matern kernel or the log-diagonals of the affine-invariant SPD Matern kernel (parameter: the
+        lengthscale itself, `series`); None when the model has none of the four forms."""
         from . import ops
         form = self._stationary_form()
         if form is not None:
@@ -602,18 +623,23 @@ class SingleTaskGP(torch.nn.Module):
             y = self.train_y.to(e.device).contiguous()
             return (lambda theta, os_, noise, mean: ops.gp_mll(e, y, theta, os_, noise, mean)), theta_fn, os_fn, False
         form = self._series_form()
-        if form is None:
-            form = self._matern_form()
-            if form is None:
-                return None
+        if form is not None:
+            c, coeff_fn, os_fn = form
+            y = self.train_y.to(c.device).contiguous()
+            base = _covar_layout(self.covar_module)[1]
+            kappa_fn = lambda: base.lengthscale.double().reshape(())                               # noqa: E731
+            return (lambda kappa, os_, noise, mean: ops.gp_mll_series(c, y, *coeff_fn(kappa), os_, noise, mean)), kappa_fn, os_fn, True
+        form = self._matern_form()
+        if form is not None:
             r, ls_fn, nu, os_fn = form
             y = self.train_y.to(r.device).contiguous()
             return (lambda ls, os_, noise, mean: ops.gp_mll_matern(r, y, ls, nu, os_, noise, mean)), ls_fn, os_fn, True
-        c, coeff_fn, os_fn = form
-        y = self.train_y.to(c.device).contiguous()
-        base = _covar_layout(self.covar_module)[1]
-        kappa_fn = lambda: base.lengthscale.double().reshape(())                               # noqa: E731
-        return (lambda kappa, os_, noise, mean: ops.gp_mll_series(c, y, *coeff_fn(kappa), os_, noise, mean)), kappa_fn, os_fn, True
+        form = self._spectral_form()
+        if form is not None:
+            a, draw, ls_fn, nu, os_fn = form
+            y = self.train_y.to(a.device).contiguous()
+            return (lambda ls, os_, noise, mean: ops.gp_mll_spd_ai_spectral(a, y, draw, ls, nu, os_, noise, mean)), ls_fn, os_fn, True
+        return None
 
     def _fast_mll_closure(self):
         """() -> (value, backward_fn) evaluating `marginal_log_likelihood` and the gradients of all parameters with one

@@ -1501,6 +1501,81 @@ def spd_ai_matern_kernel(x1, x2, phases, lam, weight, logdiag1=None, logdiag2=No
     return (f1 * f2).sum(-1) if diag else torch.mm(f1, f2.t())
 
 
+_spectral_base_held = None
+
+
+def _spectral_base_on(base, dev):
+    """(e, gamma or None) of a base draw as fp64 tensors on `dev`, uploaded once per base object and remembered for the last one"""
+    global _spectral_base_held
+    key = (id(base[0]), None if base[1] is None else id(base[1]), dev)
+    if _spectral_base_held is None or _spectral_base_held[0] != key:
+        e = torch.as_tensor(base[0], dtype=torch.float64).contiguous().to(dev)
+        gamma = None if base[1] is None else torch.as_tensor(base[1], dtype=torch.float64).contiguous().to(dev)
+        _spectral_base_held = (key, e, gamma, base[:2])      # (holding the arrays keeps their ids their own)
+    return _spectral_base_held[1], _spectral_base_held[2]
+
+
+def spd_ai_spectral_points_dkappa(base, lengthscale, nu, device=None):
+    """(e, gamma, H) and a lengthscale kappa (a number) -> (lam (L, d), w (L,), q (L,), c ()) on the device, one launch
+    (gabo_spd_ai_spectral_points_dkappa): lam and w as spd_ai_spectral_points, q = (d log w / d kappa) / 2 and the scalar c with
+    d lam / d kappa = c lam.  No gradient: q and c ARE the derivative."""
+    lib = _lib.load()
+    nu = _spectral_nu(nu)
+    dev = torch.device(device) if device is not None else _device_for()
+    e, gamma = _spectral_base_on(base, dev)
+    if gamma is None and not math.isinf(nu):
+        raise ValueError("a base draw without gamma belongs to the heat kernel (nu = math.inf)")
+    L, d = e.shape
+    lam = torch.empty(L, d, dtype=torch.float64, device=dev)
+    w, q, c = (torch.empty(s, dtype=torch.float64, device=dev) for s in ((L,), (L,), ()))
+    with _on(dev):
+        _lib.check(lib.gabo_spd_ai_spectral_points_dkappa(e.data_ptr(), _ptr(gamma), L, d, float(lengthscale), nu, lam.data_ptr(), w.data_ptr(),
+                                                          q.data_ptr(), c.data_ptr(), _stream_ptr(dev)), "gabo_spd_ai_spectral_points_dkappa")
+    return lam, w, q, c
+
+
+def spd_ai_spectral_features_dkappa(logdiag, lam, weight, q, c):
+    """The normalised features and their lengthscale derivative from stored log-diagonals, one launch (gabo_spd_ai_spectral_features_dkappa):
+    logdiag (N, L, d) = spd_ai_logdiag(x, phases), lam (L, d), weight (L,), q (L,), c (a number or a one-element tensor) as
+    spd_ai_spectral_points_dkappa returns them -> (F (N, 2 L), dF / d kappa (N, 2 L)).  F has the bits of spd_ai_spectral_features(x, phases,
+    lam, weight).  No gradient."""
+    lib = _lib.load()
+    if logdiag.dim() != 3:
+        raise RuntimeError(f"spd_ai_spectral_features_dkappa: logdiag must be (N, L, d), got {tuple(logdiag.shape)}")
+    out_device = logdiag.device
+    dev = _device_for(logdiag, lam, weight)
+    a = _prep(logdiag.detach(), dev).contiguous()
+    n, L, d = a.shape
+    lc, wc, qc = (_prep(t.detach(), dev).contiguous() for t in (lam, weight, q))
+    cc = _prep(c.detach() if torch.is_tensor(c) else torch.tensor(float(c), dtype=torch.float64), dev).reshape(1)
+    if tuple(lc.shape) != (L, d) or tuple(wc.shape) != (L,) or tuple(qc.shape) != (L,):
+        raise RuntimeError(f"lam must be ({L}, {d}), weight and q ({L},), got {tuple(lc.shape)}, {tuple(wc.shape)} and {tuple(qc.shape)}")
+    f = torch.empty(n, 2 * L, dtype=torch.float64, device=dev)
+    g = torch.empty(n, 2 * L, dtype=torch.float64, device=dev)
+    if n > 0:
+        with _on(dev):
+            _lib.check(lib.gabo_spd_ai_spectral_features_dkappa(a.data_ptr(), lc.data_ptr(), wc.data_ptr(), qc.data_ptr(), cc.data_ptr(),
+                                                                f.data_ptr(), g.data_ptr(), n, L, d, _stream_ptr(dev)),
+                       "gabo_spd_ai_spectral_features_dkappa")
+    return _out(f, out_device), _out(g, out_device)
+
+
+def spd_ai_feature_gram(f):
+    """f (N, k) -> f f^T (N, N) on the fp64 matrix pipe (gabo_spd_ai_feature_gram): exactly symmetric, the diagonal exactly 1 for rows of unit
+    norm (v / v: NaN for a row with a NaN); the bits of an entry depend on its two rows alone.  N <= GABO_GP_MLL_LARGE_MAX_N.  No gradient."""
+    lib = _lib.load()
+    if f.dim() != 2:
+        raise RuntimeError(f"spd_ai_feature_gram: f must be (N, k), got {tuple(f.shape)}")
+    out_device, dev, fc = _dense(f.detach())
+    n, k = fc.shape
+    ws = _workspace(int(lib.gabo_spd_ai_feature_gram_workspace_bytes(n, k)), dev)
+    out = torch.empty(n, n, dtype=torch.float64, device=dev)
+    with _on(dev):
+        _lib.check(lib.gabo_spd_ai_feature_gram(fc.data_ptr(), out.data_ptr(), n, k, ws.data_ptr(), ws.numel() * 8, _stream_ptr(dev)),
+                   "gabo_spd_ai_feature_gram")
+    return _out(out, out_device)
+
+
 def gp_acquisition(kstar, alpha, linv, linv_t, mean, outputscale, kxx, best_f, kind, maximize, out_sign=1.0, need_grad=True):
     """Fused GP posterior + acquisition on the strip kstar (R x n, base kernel values): -> (value R, d value / d kstar R x n or None).
     All tensors fp64 on one HIP device."""
@@ -1729,6 +1804,45 @@ def gp_mll_matern(r, y, lengthscale, nu, outputscale, noise, mean):
         _lib.check(lib.gabo_gp_mll_matern(r.data_ptr(), y.data_ptr(), n, lval, nu2, float(outputscale), float(noise), float(mean),
                                           host.data_ptr(), stream), "gabo_gp_mll_matern")
         return _mll_wait_and_read(dev, host_np)
+
+
+_mll_spectral_ws = {}
+
+
+def gp_mll_spd_ai_spectral(logdiag, y, base, lengthscale, nu, outputscale, noise, mean):
+    """One evaluation of the exact-GP marginal log likelihood with K = outputscale * k(kappa) + noise * I, k the random-phase-feature Matern /
+    heat kernel of the affine-invariant SPD metric (spd_ai_matern_kernel) at the lengthscale kappa, as ONE host call
+    (gabo_gp_mll_spd_ai_spectral): -> [ll, dll/dkappa, dll/doutputscale, dll/dnoise, dll/dmean, not_positive_definite] as Python floats.
+    logdiag: (n, L, d) = spd_ai_logdiag(x, phases) of the training points, contiguous fp64 on a HIP device, which is fixed during a fit; y: n;
+    base = (e, gamma, H) of spd_ai_spectral_base, e and gamma uploaded once per base object.  n <= GABO_GP_MLL_LARGE_MAX_N, d <= 10.  The
+    workspace and the page-locked result buffer are kept per (device, n, L, d)."""
+    lib = _lib.load()
+    nu = _spectral_nu(nu)
+    dev = logdiag.device
+    if logdiag.dim() != 3 or y.numel() != logdiag.shape[0] or not logdiag.is_contiguous() or not y.is_contiguous():
+        raise RuntimeError("gp_mll_spd_ai_spectral: logdiag must be a contiguous (n, L, d) tensor and y a contiguous vector of n targets")
+    _require(dev, logdiag=logdiag, y=y)
+    n, L, d = logdiag.shape
+    e, gamma = _spectral_base_on(base, dev)
+    if tuple(e.shape) != (L, d) or (gamma is None) != math.isinf(nu):
+        raise RuntimeError(f"gp_mll_spd_ai_spectral: the base draw has e {tuple(e.shape)} and {'no ' if gamma is None else ''}gamma; "
+                           f"logdiag is {(n, L, d)} and nu = {nu}")
+    key = (dev, n, L, d)
+    ent = _mll_spectral_ws.get(key)
+    if ent is None:
+        wsb = int(lib.gabo_gp_mll_spd_ai_spectral_workspace_bytes(n, L, d))
+        if wsb == 0:
+            raise RuntimeError(f"gp_mll_spd_ai_spectral: (n, L, d) = {(n, L, d)} is outside 1 <= n <= {_lib.GABO_GP_MLL_LARGE_MAX_N}, 2 <= d <= 10")
+        if len(_mll_spectral_ws) > 4:
+            _mll_spectral_ws.clear()
+        import ctypes
+        ent = _mll_spectral_ws[key] = (_workspace(wsb, dev), _pinned(8).zero_(), (ctypes.c_double * 7)())
+    ws, host, out = ent
+    with _on(dev):
+        _lib.check(lib.gabo_gp_mll_spd_ai_spectral(logdiag.data_ptr(), y.data_ptr(), e.data_ptr(), _ptr(gamma), n, L, d, nu, float(lengthscale),
+                                                   float(outputscale), float(noise), float(mean), out, ws.data_ptr(), ws.numel() * 8,
+                                                   host.data_ptr(), 8, _stream_ptr(dev)), "gabo_gp_mll_spd_ai_spectral")
+    return [out[0], out[6], out[2], out[3], out[4], out[5]]
 
 
 def gram_extreme_eigenvalues(e, thetas):

@@ -372,6 +372,45 @@ int gabo_spd_ai_spectral_features(const double* x_mandel, const double* phases, 
                                   int64_t n, int64_t L, int d, gabo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The surrogate fit of those kernels with ONE host call per evaluation (csrc/spd_ai_spectral_fit.hip).  During a fit the log-diagonals
+ * a (n x L x d, gabo_spd_ai_logdiag) are fixed; the spectral points move with the lengthscale kappa as lam_l = e_l g(kappa), so that
+ * d lam_l / d kappa = c lam_l with one scalar c:  heat (nu = inf) lam = e / kappa, c = -1 / kappa;  Matern lam = e sqrt((nu / kappa^2 + b) /
+ * gamma_l), b = d (d^2 - 1) / 96, c = -nu / (kappa (nu + b kappa^2)).  w_l = prod_{i<j} tanh(pi |lam_li - lam_lj|),
+ * q_l = (d log w_l / d kappa) / 2 = c sum_{i<j} pi |D_ij| / sinh(2 pi |D_ij|) (each term -> 1/2 for D_ij -> 0; no division by w).
+ *   e: L x d, gamma: L (NULL and ignored for nu = inf) - the base draw, on the device.
+ * gabo_spd_ai_spectral_points_dkappa: lam (L x d), weight (L), q (L) and c (ONE double) on the device, a lane per feature; the operations of
+ *   the formulas above in their order.
+ * gabo_spd_ai_spectral_features_dkappa: from a, lam, weight, q, c (all on the device, c one double):  fhat = the normalised features Fh
+ *   (n x 2L) with the bits gabo_spd_ai_spectral_features returns for the points `a` came from and the same lam, weight;
+ *   gdot = d Fh / d kappa (n x 2L):  with f the raw features, s_i = |f_i|^2,  df_cos = q f_cos - c theta f_sin,  df_sin = q f_sin + c theta f_cos,
+ *   gdot_i = df_i / sqrt(s_i) - Fh_i (sum_l q_l (f_cos,il^2 + f_sin,il^2)) / s_i;  both row sums in one fixed order.
+ * gabo_spd_ai_feature_gram: out = f f^T (n x n) for f: n x k row-major, on the fp64 matrix pipe; exactly symmetric, the diagonal v / v
+ *   (1, or NaN for a row with a NaN).  The bits of out_ij depend on rows i and j of f and on k alone, not on n.
+ *   workspace: *_workspace_bytes(n, k) = ceil(n / 16) 16 * ceil(k / 16) 16 doubles, the zero-padded copy of f the launch reads.
+ * gabo_gp_mll_spd_ai_spectral: the points, features and Gram launches above, gabo_gp_mll_gram (gabo_gp_mll_large above GABO_GP_MLL_MAX_N)
+ *   on Ky = outputscale K + noise I, and sum_{i != j} W_ij (gdot_i . fhat_j) tile by tile in a fixed order, back to back on `stream`; waits.
+ *   a, y: device; nu: positive, or infinity for the heat kernel; lengthscale, outputscale, noise, mean: host scalars.
+ *   out_host (7 doubles): [ll, 0, d ll/d outputscale, d ll/d noise, d ll/d mean, not-positive-definite flag, d ll/d kappa];
+ *   out_host[0], [2..5] have the bits of gabo_gp_mll_gram (gabo_gp_mll_large) on the matrix of gabo_spd_ai_feature_gram; with the flag set
+ *   every other output is 0.  Two calls return the same bits.  A NaN in `a` gives a NaN row and column of K and what the likelihood
+ *   launch returns on that; nothing faults and nothing is reported.
+ *   workspace: device, *_workspace_bytes(n, L, d) (0 for arguments the call refuses); pinned: >= 7 doubles of page-locked host memory.
+ * GABO_ERR_DIM for d outside 2 ... 10 and (the Gram and likelihood entries) n outside 1 ... GABO_GP_MLL_LARGE_MAX_N; GABO_ERR_ARG for a null
+ * pointer (gamma with nu = inf excepted), n < 1, L < 1 or k < 1, L > 2^24, a lengthscale that is not positive and finite, a nu that is not
+ * positive and a short workspace or pinned buffer - all before any HIP call. */
+int gabo_spd_ai_spectral_points_dkappa(const double* e, const double* gamma, int64_t L, int d, double lengthscale, double nu, double* lam,
+                                       double* weight, double* q, double* c, gabo_stream_t stream);
+int gabo_spd_ai_spectral_features_dkappa(const double* a, const double* lam, const double* weight, const double* q, const double* c,
+                                         double* fhat, double* gdot, int64_t n, int64_t L, int d, gabo_stream_t stream);
+size_t gabo_spd_ai_feature_gram_workspace_bytes(int64_t n, int64_t k);
+int gabo_spd_ai_feature_gram(const double* f, double* out, int64_t n, int64_t k, void* workspace, size_t workspace_bytes,
+                             gabo_stream_t stream);
+size_t gabo_gp_mll_spd_ai_spectral_workspace_bytes(int64_t n, int64_t L, int d);
+int gabo_gp_mll_spd_ai_spectral(const double* a, const double* y, const double* e, const double* gamma, int64_t n, int64_t L, int d, double nu,
+                                double lengthscale, double outputscale, double noise, double mean, double* out_host, void* workspace,
+                                size_t workspace_bytes, double* pinned, size_t pinned_doubles, gabo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Extreme eigenvalues of the kernel matrices of a kernel-parameter study, all (point set, parameter) pairs in one launch
  * (examples/kernels/spd/spd_gaussian_kernel_parameters.py:84-125 and examples/kernels/sphere/sphere_gaussian_kernel_parameters.py:62-112:
  * per pair one kernel.forward and one np.linalg.eig on the host, of which the minimum is kept).
