@@ -135,6 +135,8 @@ SIGNATURES = {
     "gabo_gp_mll_matern": (_I, [_P, _P, _I64, _D, _I, _D, _D, _D, _P, _P]),
     "gabo_spd_ai_logdiag": (_I, [_P, _P, _P, _I64, _I64, _I, _P]),
     "gabo_spd_ai_spectral_features": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I, _P]),
+    "gabo_spd_ai_spectral_features_backward_workspace_bytes": (_SZ, [_I64, _I64, _I]),
+    "gabo_spd_ai_spectral_features_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _I64, _I64, _I, _P]),
     "gabo_spd_ai_spectral_points_dkappa": (_I, [_P, _P, _I64, _I, _D, _D, _P, _P, _P, _P, _P]),
     "gabo_spd_ai_spectral_features_dkappa": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I, _P]),
     "gabo_spd_ai_feature_gram_workspace_bytes": (_SZ, [_I64, _I64]),

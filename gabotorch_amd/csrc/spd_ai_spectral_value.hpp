@@ -1,6 +1,7 @@
-// What the two translation units of the affine-invariant SPD Matern features share (spd_ai_spectral.hip: the features from the points;
-// spd_ai_spectral_fit.hip: the features and their lengthscale derivative from stored log-diagonals): the block shape, which fixes the order
-// of the row sums, and the one function that turns (theta, -rho . a, w) into a raw feature pair.  Both kernels must produce the same bits.
+// What the translation units of the affine-invariant SPD Matern features share (spd_ai_spectral.hip: the features from the points;
+// spd_ai_spectral_fit.hip: the features and their lengthscale derivative from stored log-diagonals; spd_ai_spectral_backward.hip: the
+// x-gradient): the block shape, which fixes the order of the row sums, and the one function that turns (theta, -rho . a, w) into a raw
+// feature pair.  The first two must produce the same bits.
 #pragma once
 #include "gabo_device.hpp"
 
@@ -14,7 +15,7 @@ constexpr int kSpectralMaxDim = 10;
 struct SpectralPair {
     double c, s;
 };
-static __device__ __attribute__((noinline)) SpectralPair spectral_feature_value(double theta, double la, double w) {
+[[maybe_unused]] static __device__ __attribute__((noinline)) SpectralPair spectral_feature_value(double theta, double la, double w) {
     const double amp = __builtin_sqrt(w) * exp(la);
     double sn, cs;
     sincos(theta, &sn, &cs);

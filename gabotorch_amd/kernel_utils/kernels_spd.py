@@ -159,15 +159,19 @@ class SpdAffineInvariantMaternKernel(Kernel):
     (exp(-r^2 / (2 lengthscale^2)) is the flat-space limit of the heat kernel, the convention of the sphere and flat-SPD Matern classes), no
     beta_min.  nu is fixed, not a parameter; the random draw (seed) is fixed at construction and shared by every lengthscale.
     forward takes the cheapest route that supports the gradients asked for: none - one fused launch per point set; the lengthscale only - the
-    log-diagonals from one launch, remembered for the last point set (a fit computes them once), then element-wise torch; x - a plain torch
-    composition (first order, slow).  dim <= 10 on the device."""
+    log-diagonals from one launch, remembered for the last point set (a fit computes them once), then element-wise torch; x with a lengthscale
+    that does not require grad (an acquisition maximiser over a fitted, frozen model) - the fused launch, and one backward launch pair per
+    point set and backward() (ops.spd_ai_spectral_features_backward; first order); x together with the lengthscale, or x_grad="torch" - a plain
+    torch composition (first order, slow).  dim <= 10 on the device."""
 
-    def __init__(self, dim, nu=2.5, num_features=1024, seed=0, **kwargs):
+    def __init__(self, dim, nu=2.5, num_features=1024, seed=0, x_grad="launch", **kwargs):
         base = ops.spd_ai_spectral_base(dim, num_features, nu, seed)          # (validates dim, num_features and nu)
+        if x_grad not in ("launch", "torch"):
+            raise ValueError(f"x_grad must be 'launch' or 'torch', got {x_grad!r}")
         self.has_lengthscale = True
         super().__init__(has_lengthscale=True, ard_num_dims=None, **kwargs)
         self.dim, self.nu, self.num_features, self.seed = dim, float(nu), num_features, seed
-        self.spectral_base = base
+        self.spectral_base, self.x_grad = base, x_grad
         self._phases = {}               # device -> H (L, d, d)
         self._logdiag_held = None
 
@@ -211,9 +215,10 @@ class SpdAffineInvariantMaternKernel(Kernel):
         p1, shape1 = self._points(x1)
         p2, shape2 = (p1, shape1) if same else self._points(x2)
         if x1.dim() == 2 and x2.dim() == 2:
-            return ops.spd_ai_matern_kernel(p1, p2, phases, lam, w, logdiag1=logdiag_of(p1), logdiag2=None if same else logdiag_of(p2))
-        f1 = shape1(ops.spd_ai_spectral_features(p1, phases, lam, w, logdiag=logdiag_of(p1)))
-        f2 = f1 if same else shape2(ops.spd_ai_spectral_features(p2, phases, lam, w, logdiag=logdiag_of(p2))).to(f1.device)
+            return ops.spd_ai_matern_kernel(p1, p2, phases, lam, w, logdiag1=logdiag_of(p1), logdiag2=None if same else logdiag_of(p2),
+                                            x_grad=self.x_grad)
+        f1 = shape1(ops.spd_ai_spectral_features(p1, phases, lam, w, logdiag=logdiag_of(p1), x_grad=self.x_grad))
+        f2 = f1 if same else shape2(ops.spd_ai_spectral_features(p2, phases, lam, w, logdiag=logdiag_of(p2), x_grad=self.x_grad)).to(f1.device)
         return f1 @ f2.transpose(-1, -2)
 
 

@@ -1452,21 +1452,8 @@ def _spectral_logdiag_torch(x, phases):
     return 2.0 * torch.log(torch.diagonal(torch.linalg.cholesky(0.5 * (s + s.transpose(-1, -2))), dim1=-2, dim2=-1))
 
 
-def spd_ai_spectral_features(x, phases, lam, weight, logdiag=None):
-    """Normalised random phase features F (N, 2 L) of the points x (N, d(d+1)/2), |F_i| = 1, for phases (L, d, d), spectral points lam (L, d)
-    and weights (L,).  The cheapest route that supports the gradients asked for:
-      - nothing requires grad, no `logdiag`: ONE fused launch (gabo_spd_ai_spectral_features); the log-diagonals are never stored;
-      - `logdiag` (= spd_ai_logdiag(x, phases)) given: element-wise torch operations on it, differentiable in lam and weight (so in the
-        lengthscale they come from); x is not looked at;
-      - x requires grad: a plain torch composition through torch.linalg.cholesky of the N L matrices H^T X H - first order, and slow."""
-    if logdiag is not None:
-        return _spectral_features_torch(logdiag, lam.to(logdiag), weight.to(logdiag))
-    d = _spectral_points_input(x, "spd_ai_spectral_features")
-    if torch.is_grad_enabled() and x.requires_grad:
-        xd = x.double()
-        return _spectral_features_torch(_spectral_logdiag_torch(xd, phases.to(xd)), lam.to(xd), weight.to(xd))
-    if torch.is_grad_enabled() and (lam.requires_grad or weight.requires_grad):
-        return _spectral_features_torch(spd_ai_logdiag(x, phases).to(lam.device), lam.double(), weight.double())
+def _spectral_features_launch(x, phases, lam, weight, d):
+    """the fused forward launch: no gradient"""
     lib = _lib.load()
     out_device = x.device
     dev = _device_for(x, phases, lam, weight)
@@ -1483,12 +1470,95 @@ def spd_ai_spectral_features(x, phases, lam, weight, logdiag=None):
     return _out(out, out_device)
 
 
-def spd_ai_matern_kernel(x1, x2, phases, lam, weight, logdiag1=None, logdiag2=None, diag=False):
-    """k(x1_i, x2_j) = <F(x1_i), F(x2_j)> (N1, N2) with F = spd_ai_spectral_features (routes and gradients: see there): a Monte-Carlo
-    approximation, error O(1 / sqrt L), of the Riemannian Matern / heat kernel of the affine-invariant metric that is positive semi-definite for
-    every sample.  `x2 is x1`: one feature call, and the matrix is exactly symmetric with an exactly unit diagonal.  diag=True: the diagonal
-    (N1 == N2), exactly 1 when x2 is x1."""
-    f1 = spd_ai_spectral_features(x1, phases, lam, weight, logdiag=logdiag1)
+_spectral_backward_ws = {}
+
+
+def spd_ai_spectral_features_backward(x, phases, lam, fhat, grad_out):
+    """The x-gradient of the normalised features, the launch alone (gabo_spd_ai_spectral_features_backward: the factorisations once more
+    and one small congruence per point, no tape): x (N, d(d+1)/2), phases (L, d, d), lam (L, d), fhat (N, 2 L) =
+    spd_ai_spectral_features(x, phases, lam, weight), grad_out (N, 2 L) the upstream gradient of fhat -> d <grad_out, fhat> / d x (N, d(d+1)/2)
+    on x's device.  The weights cancel.  2 <= d <= 10, no gradient of its own.  A NaN or non-SPD row of x gives NaN in its own row.  The
+    workspace is kept per (device, N, L, d)."""
+    if x.dim() != 2:
+        raise RuntimeError(f"spd_ai_spectral_features_backward: x must be (N, d(d+1)/2) Mandel vectors (no batch dimensions), got {tuple(x.shape)}")
+    d = _mandel_dim(x.shape[-1])
+    if phases.dim() != 3 or tuple(phases.shape[1:]) != (d, d):
+        raise RuntimeError(f"spd_ai_spectral_features_backward: phases must be (L, {d}, {d}), got {tuple(phases.shape)}")
+    n, L = x.shape[0], phases.shape[0]
+    if tuple(lam.shape) != (L, d):
+        raise RuntimeError(f"spd_ai_spectral_features_backward: lam must be ({L}, {d}), got {tuple(lam.shape)}")
+    if tuple(fhat.shape) != (n, 2 * L) or tuple(grad_out.shape) != (n, 2 * L):
+        raise RuntimeError(f"spd_ai_spectral_features_backward: fhat and grad_out must be ({n}, {2 * L}), got {tuple(fhat.shape)} and "
+                           f"{tuple(grad_out.shape)}")
+    lib = _lib.load()
+    out_device = x.device
+    dev = _device_for(x, phases, lam, fhat, grad_out)
+    xc = _prep(x.detach(), dev).contiguous()
+    ht = _spectral_phases(phases, dev, d)
+    lc, fc, gc = (_prep(t.detach(), dev).contiguous() for t in (lam, fhat, grad_out))
+    gx = (torch.zeros if L == 0 else torch.empty)(n, x.shape[-1], dtype=torch.float64, device=dev)          # (no feature: no launch)
+    key = (dev, n, L, d)
+    ws = _spectral_backward_ws.get(key)
+    if ws is None:
+        if len(_spectral_backward_ws) > 4:
+            _spectral_backward_ws.clear()
+        # (0 bytes for a shape that the call below refuses)
+        ws = _spectral_backward_ws[key] = _workspace(int(lib.gabo_spd_ai_spectral_features_backward_workspace_bytes(n, L, d)), dev)
+    with _on(dev):
+        _lib.check(lib.gabo_spd_ai_spectral_features_backward(xc.data_ptr(), ht.data_ptr(), lc.data_ptr(), fc.data_ptr(), gc.data_ptr(),
+                                                              gx.data_ptr(), ws.data_ptr(), ws.numel() * 8, n, L, d, _stream_ptr(dev)),
+                   "gabo_spd_ai_spectral_features_backward")
+    return _out(gx, out_device)
+
+
+class _SpectralFeaturesFunction(torch.autograd.Function):
+    """The fused feature launch with the backward launch as its x-gradient: first order, gradients for x only."""
+
+    @staticmethod
+    def forward(ctx, x, phases, lam, weight, d):
+        fhat = _spectral_features_launch(x, phases, lam, weight, d)
+        ctx.save_for_backward(x, fhat)
+        ctx.phases, ctx.lam = phases, lam.detach()
+        return fhat
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, fhat = ctx.saved_tensors
+        return spd_ai_spectral_features_backward(x, ctx.phases, ctx.lam, fhat, grad_out).to(x.dtype), None, None, None, None
+
+
+def spd_ai_spectral_features(x, phases, lam, weight, logdiag=None, x_grad="launch"):
+    """Normalised random phase features F (N, 2 L) of the points x (N, d(d+1)/2), |F_i| = 1, for phases (L, d, d), spectral points lam (L, d)
+    and weights (L,).  The cheapest route that supports the gradients asked for:
+      - nothing requires grad, no `logdiag`: ONE fused launch (gabo_spd_ai_spectral_features); the log-diagonals are never stored;
+      - `logdiag` (= spd_ai_logdiag(x, phases)) given: element-wise torch operations on it, differentiable in lam and weight (so in the
+        lengthscale they come from); x is not looked at;
+      - x requires grad and neither lam nor weight does: the fused launch, with spd_ai_spectral_features_backward (one launch pair) as its
+        gradient - first order, nothing kept but x and F;
+      - x requires grad together with lam or weight, or x_grad="torch": a plain torch composition through torch.linalg.cholesky of the N L
+        matrices H^T X H - first order, and slow."""
+    if x_grad not in ("launch", "torch"):
+        raise ValueError(f"x_grad must be 'launch' or 'torch', got {x_grad!r}")
+    if logdiag is not None:
+        return _spectral_features_torch(logdiag, lam.to(logdiag), weight.to(logdiag))
+    d = _spectral_points_input(x, "spd_ai_spectral_features")
+    if torch.is_grad_enabled() and x.requires_grad:
+        if x_grad == "launch" and not (lam.requires_grad or weight.requires_grad):
+            return _SpectralFeaturesFunction.apply(x, phases, lam, weight, d)
+        xd = x.double()
+        return _spectral_features_torch(_spectral_logdiag_torch(xd, phases.to(xd)), lam.to(xd), weight.to(xd))
+    if torch.is_grad_enabled() and (lam.requires_grad or weight.requires_grad):
+        return _spectral_features_torch(spd_ai_logdiag(x, phases).to(lam.device), lam.double(), weight.double())
+    return _spectral_features_launch(x, phases, lam, weight, d)
+
+
+def spd_ai_matern_kernel(x1, x2, phases, lam, weight, logdiag1=None, logdiag2=None, diag=False, x_grad="launch"):
+    """k(x1_i, x2_j) = <F(x1_i), F(x2_j)> (N1, N2) with F = spd_ai_spectral_features (routes and gradients, `x_grad` among them: see there): a
+    Monte-Carlo approximation, error O(1 / sqrt L), of the Riemannian Matern / heat kernel of the affine-invariant metric that is positive
+    semi-definite for every sample.  `x2 is x1`: one feature call, and the matrix is exactly symmetric with an exactly unit diagonal.
+    diag=True: the diagonal (N1 == N2), exactly 1 when x2 is x1."""
+    f1 = spd_ai_spectral_features(x1, phases, lam, weight, logdiag=logdiag1, x_grad=x_grad)
     if x2 is x1:
         k = torch.mm(f1, f1.t())
         dg = k.diagonal()
@@ -1497,7 +1567,7 @@ def spd_ai_matern_kernel(x1, x2, phases, lam, weight, logdiag1=None, logdiag2=No
             return unit
         k = 0.5 * (k + k.t())
         return torch.where(torch.eye(k.shape[0], dtype=torch.bool, device=k.device), unit.unsqueeze(-1).expand_as(k), k)
-    f2 = spd_ai_spectral_features(x2, phases, lam, weight, logdiag=logdiag2).to(f1.device)
+    f2 = spd_ai_spectral_features(x2, phases, lam, weight, logdiag=logdiag2, x_grad=x_grad).to(f1.device)
     return (f1 * f2).sum(-1) if diag else torch.mm(f1, f2.t())
 
 

@@ -372,6 +372,25 @@ int gabo_spd_ai_spectral_features(const double* x_mandel, const double* phases, 
                                   int64_t n, int64_t L, int d, gabo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The x-gradient of those features (csrc/spd_ai_spectral_backward.hip): for fhat = the output of gabo_spd_ai_spectral_features (n x 2L) and
+ * grad_out = the upstream gradient of fhat (n x 2L), grad_x (n x d(d+1)/2) = d <grad_out, fhat> / d x_mandel, in closed form and without a
+ * tape.  With s_i = <grad_out_i, fhat_i> and, per (point, feature),  P = (g_c - s f_c) f_c + (g_s - s f_s) f_s,  R = g_s f_c - g_c f_s,
+ * gb_k = -rho_k P + lam_lk R  (f, g the cos / sin entries of fhat and grad_out; weight and the row norm cancel):
+ *   Gamma_i = G^-T (sum_l sum_k gb_ilk v_ilk v_ilk^T / |v_ilk|^2) G^-1,  X_i = G G^T, v_ilk row k of H_l^T G after the Gram-Schmidt pass of the
+ *   forward launch (a_k = log |v_k|^2);  grad_x row i = Gamma_i in Mandel layout (off-diagonals times sqrt 2).
+ * Two launches back to back on `stream`: the factorisations once more, a lane per (point, feature), with the block's part of the inner sum by
+ * a halving tree -> workspace (n x ceil(L / 128) x d(d+1)/2); then per point the parts in ascending order, G^-1 and the congruence.  No
+ * atomics and no counter: two calls return the same bits, and the bits of row i depend on X_i, row i of fhat and grad_out, phases, lam and
+ * L alone (not on n or the other points).  A NaN or non-SPD X_i gives NaN in row i of grad_x and nowhere else; nothing is reported.
+ *   workspace: device, *_workspace_bytes(n, L, d) (0 for arguments the call refuses); no need to clear it.
+ * GABO_ERR_DIM for d outside 2 ... 10; GABO_ERR_ARG for n < 0, L < 0, a null pointer, n ceil(L / 128) >= 2^31 or a short workspace;
+ * GABO_OK without a launch for n = 0 or L = 0 - all before any HIP call. */
+size_t gabo_spd_ai_spectral_features_backward_workspace_bytes(int64_t n, int64_t L, int d);
+int gabo_spd_ai_spectral_features_backward(const double* x_mandel, const double* phases, const double* lam, const double* fhat,
+                                           const double* grad_out, double* grad_x, void* workspace, size_t workspace_bytes, int64_t n,
+                                           int64_t L, int d, gabo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * The surrogate fit of those kernels with ONE host call per evaluation (csrc/spd_ai_spectral_fit.hip).  During a fit the log-diagonals
  * a (n x L x d, gabo_spd_ai_logdiag) are fixed; the spectral points move with the lengthscale kappa as lam_l = e_l g(kappa), so that
  * d lam_l / d kappa = c lam_l with one scalar c:  heat (nu = inf) lam = e / kappa, c = -1 / kappa;  Matern lam = e sqrt((nu / kappa^2 + b) /
